@@ -16,6 +16,13 @@ barrier + synchronize around the timed region, max time over ranks.  Launched ei
 ``torch.distributed.run --nproc-per-node N bench.py --gpus N`` or as plain ``bench.py --gpus N``,
 which starts the N ranks itself (torch.distributed.run on 127.0.0.1) before touching the GPU.
 
+A plain run sets up, warms up, times the ``--steps`` steps and prints the headline figure
+(``value``, ``ms_per_step``).  ``--full`` adds everything else the rollout bench measures, in runs of
+their own after the timed one: the stamped re-run and the launch-by-launch replay (per-kernel times,
+rooflines), the PMC provenance and the CPU baseline.  ``--dump-outputs DIR`` writes what the timed
+path computed in its last step as ``DIR/<name>.npy``; with the same arguments the inputs are the
+same from run to run, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -147,6 +154,31 @@ def pmc_mfma_busy(kernel, cus, config="headline"):
         return None
 
 
+DUMP_MAX_BYTES = 48 << 20   # all arrays of one --dump-outputs together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``dirname/<name>.npy`` in float32 (float64 stays).
+    Each array gets an equal share of DUMP_MAX_BYTES; a larger one is cut to a fixed sample of its
+    leading (batch) axis: sorted indices drawn without replacement by numpy's default_rng(0), the same
+    for every run and build."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        row = t[0].numel() * t.element_size()
+        if row > share:
+            raise SystemExit(f"bench: --dump-outputs: one row of {name} ({row} B) exceeds its share {share} B")
+        if t.shape[0] * row > share:
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], share // row, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,7 +199,16 @@ def parse():
     ap.add_argument("--size", type=int, default=None, help="canvas (default: the config's)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0,
                     help="wall budget of the CPU baseline (rank 0, N=1 only), split over its entries")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="rollout: after the timed steps also run what the headline figure does not need "
+                         "(the stamped re-run and the launch-by-launch replay for the per-kernel and "
+                         "roofline figures, the PMC provenance, the CPU baseline) and report it in the "
+                         "line.  Off by default: a plain run sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32; rank 0; a fixed seeded sample along the batch axis where "
+                         "an array would not fit the size cap)")
     ap.add_argument("--dist-backend", default=None, choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the default for N>1) on a node; gloo only to rehearse N>1 ranks "
                          "on one GPU.  Given explicitly at N=1, a world-1 process group of that backend "
@@ -379,6 +420,7 @@ def main_train(args, dev, world, rank):
     stab_rng = random.Random(4242 + rank)
     cells = [0]
     ar_bytes = [0]   # bytes of the last flat gradient all-reduce (0: no process group)
+    last_state = [None]   # the last iteration's rolled-out batch (--dump-outputs)
     # GNCA_TRAIN_PHASES=1 (measurement only): synchronise at the phase boundaries and report the
     # mean wall time of each phase of an iteration on stderr
     phase_t = {} if os.environ.get("GNCA_TRAIN_PHASES") else None
@@ -438,6 +480,7 @@ def main_train(args, dev, world, rank):
         opt.step()
         pool.replace(idx, state.detach())
         mark("allreduce+adam+pool", tp)
+        last_state[0] = state.detach()
         return loss
 
     for w_ in range(args.warmup):
@@ -468,6 +511,10 @@ def main_train(args, dev, world, rank):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
         dist.all_reduce(tot)
+    if rank == 0 and args.dump_outputs:   # what the last iteration left: its batch, loss and the parameters
+        dump_outputs(args.dump_outputs, {
+            "state": last_state[0], "loss": loss,
+            "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     if rank == 0:
         extra = ", damage curriculum (config.json), stability phase (24 steps, loss < 0.01)" \
             if twl["damage"] else ""
@@ -543,6 +590,8 @@ def main_regen(args, dev):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     n = args.steps + 1
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"state": state, "attention": attn})
     from graph_neural_cellular_automata_amd import _lib as L
     from graph_neural_cellular_automata_amd import step as S
     line = {
@@ -673,13 +722,14 @@ def main():
             L.check(rc, "gnca_rollout_ex_f32")
             cur = nxt
 
-    # buffers of the stamped re-run (below), allocated before the GPU warm-up: an allocation between
-    # the warm-up and the timed run (or between the timed and the stamped run) idles the GPU, and the
-    # run after it starts at ramping clocks
+    # --full: buffers of the stamped re-run (below), allocated before the GPU warm-up: an allocation
+    # between the warm-up and the timed run (or between the timed and the stamped run) idles the GPU,
+    # and the run after it starts at ramping clocks
     cap = 16384
     nsub = S.rollout_subs(make_desc(wl, B, H, H, offsets_table[:K], rank, args.warmup))
-    stamps = torch.zeros(args.steps * nsub * 4 * cap, dtype=torch.int64, device=dev)
-    dst2 = torch.empty_like(x)
+    if args.full:
+        stamps = torch.zeros(args.steps * nsub * 4 * cap, dtype=torch.int64, device=dev)
+        dst2 = torch.empty_like(x)
     # warmup: the rollout's first W steps, untimed; the K timed steps continue from their state (and
     # fire counters), as one rollout of W + K steps
     start = x
@@ -723,7 +773,8 @@ def main():
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
-    stamped_ms = stamped_rollout()
+    if args.full:
+        stamped_ms = stamped_rollout()
     cpu_dev = dev if args.dist_backend == "nccl" else "cpu"
     ranks_seen = 1
     rank_sums = [float(out.double().sum())]
@@ -739,6 +790,34 @@ def main():
         rank_sums = [float(v.item()) for v in sums]
     cells = B * H * H
     value = cells * args.steps * world / el
+    metric = ("cell-updates/sec (B·H·W·steps) for 16ch 72×72 rollout at 1/2/4/8 MI355X" if C == 16
+              else f"cell-updates/sec (B·H·W·steps) for {C}ch {H}×{H} rollout")
+    wdesc = ("trained nca_latest.pt" if wl["graph"] and C == 16 else
+             "trained classic nca_epoch980.pt" if not wl["graph"] else
+             "seeded random init (W2 ~ N(0,0.02))")
+    ms = el / args.steps * 1e3
+    line = {
+        "metric": metric,
+        "value": value, "unit": "cell-updates/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "gpu_warmup": {"ms": args.gpu_warmup_ms, "steps": gw_steps},
+        "ms_per_step": ms,
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
+        "data": f"synthetic state (RGB,alpha~U(0,1), hidden~N(0,1)); {wdesc} weights from the "
+                f"committed golden fixture",
+        "config": {"workload": wl["name"], "config": args.config,
+                   "channels": C, "hidden": HD, "height": H, "width": H,
+                   "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}"},
+        "ranks_seen": ranks_seen, "backend": (args.dist_backend if (world > 1 or args.pg1) else None),
+        "rank_state_checksums": rank_sums, "full": args.full,
+    }
+    if rank == 0 and args.dump_outputs:   # the rollout's final state: what the timed call returned
+        dump_outputs(args.dump_outputs, {"state": out})
+    if not args.full:   # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1 or args.pg1:
+            dist.destroy_process_group()
+        return
 
     # --- per-kernel durations of the timed rollout itself: the same rollout again (same start state,
     #     offsets and fire counters; final state checked bitwise) through gnca_rollout_stamped_f32,
@@ -911,25 +990,7 @@ def main():
         cpu = None
         if world == 1 and not args.no_cpu:
             cpu = cpu_baseline(args.cpu_seconds)
-        metric = ("cell-updates/sec (B·H·W·steps) for 16ch 72×72 rollout at 1/2/4/8 MI355X" if C == 16
-                  else f"cell-updates/sec (B·H·W·steps) for {C}ch {H}×{H} rollout")
-        wdesc = ("trained nca_latest.pt" if wl["graph"] and C == 16 else
-                 "trained classic nca_epoch980.pt" if not wl["graph"] else
-                 "seeded random init (W2 ~ N(0,0.02))")
-        ms = el / args.steps * 1e3
-        line = {
-            "metric": metric,
-            "value": value, "unit": "cell-updates/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "gpu_warmup": {"ms": args.gpu_warmup_ms, "steps": gw_steps},
-            "ms_per_step": ms,
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
-            "data": f"synthetic state (RGB,alpha~U(0,1), hidden~N(0,1)); {wdesc} weights from the "
-                    f"committed golden fixture",
-            "config": {"workload": wl["name"], "config": args.config,
-                       "channels": C, "hidden": HD, "height": H, "width": H,
-                       "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}"},
-            "ranks_seen": ranks_seen, "backend": (args.dist_backend if (world > 1 or args.pg1) else None),
-            "rank_state_checksums": rank_sums,
+        line.update({
             "k1_k2_ms_vs_step": (k1_ms + k2_ms) / ms,   # > 1 only where sub-batches overlap K2 with K1
             "device_timeline": {"stamped_rollout_ms_per_step": stamped_ms,
                                 "k1_tail_frac": float(np.mean(tails)) if tails else None,
@@ -939,7 +1000,7 @@ def main():
                                 "gaps_minus_overlap_ms_per_step": span_ms - k1_ms - k2_ms},
             "roofline": roof, "roofline_k2": roof_k2, "cpu_baseline": cpu,
             "pmc_provenance": pmc_provenance(pmc_key, L.LIB_PATH),
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1 or args.pg1:
         dist.destroy_process_group()

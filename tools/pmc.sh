@@ -1,13 +1,14 @@
 #!/bin/bash
 # PMC passes over a short bench run, one counter group per rocprofv3 invocation (no tracing
-# domains mixed with --pmc).  Output: gpurun_out/pmc/<pass>/...counter_collection.csv
+# domains mixed with --pmc).  Output: $PMC_OUT/p<pass>/...counter_collection.csv (default
+# bench_out/pmc, or under $GNCA_OUT).  The bench runs with --full: the passes also count the kernels
+# of the stamped re-run and of the launch-by-launch replay (the plain K1 and every step's K2).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/pmc
-ARGS="${PMC_CMD:-python3 bench.py --steps 4 --warmup 1 --no-cpu ${BENCH_ARGS:-}}"
+ARGS="${PMC_CMD:-python3 bench.py --steps 4 --warmup 1 --full --no-cpu ${BENCH_ARGS:-}}"
 REGEX="${PMC_REGEX:-gnca_k}"
-OUT="${PMC_OUT:-gpurun_out/pmc}"
+OUT="${PMC_OUT:-${GNCA_OUT:-bench_out}/pmc}"
 mkdir -p "$OUT"
 # PMC_PASSES: the pass numbers to run (default every pass), e.g. "1 2 4"
 i=0

@@ -30,7 +30,7 @@ res = {"fetch_correction": 2.0,
        # rollout launches of each kernel per CA step when the passes ran (2: the sub-batch pipeline)
        "launches_per_step": int(os.environ.get("PMC_LAUNCHES_PER_STEP", "1")),
        "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over "
-                 "`python3 bench.py --steps 4 --warmup 1 --no-cpu` (tools/pmc.sh); "
+                 "`python3 bench.py --steps 4 --warmup 1 --full --no-cpu` (tools/pmc.sh); "
                  "FETCH_SIZE x2 per tools/ubench/fetch_calib.hip",
        # sha256[:16] of the libgnca.so the passes ran (set by the session script), so that a bench line
        # can tell whether these counters belong to the build it timed

@@ -1,5 +1,5 @@
-"""Per-kernel average durations from a rocprofv3 kernel trace of `bench.py` next to the bench
-line's own HIP-event averages (roofline k1_ms / k2_ms).  The trace of `bench.py --no-cpu` holds,
+"""Per-kernel average durations from a rocprofv3 kernel trace of `bench.py --full` next to the bench
+line's own HIP-event averages (roofline k1_ms / k2_ms).  The trace of `bench.py --full --no-cpu` holds,
 per kernel, W warmup launches, then K timed and K replayed launches (bench.py's K1/K2 averages are
 over the replayed launches, which repeat the timed ones' work).
 

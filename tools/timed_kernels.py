@@ -1,6 +1,6 @@
-"""The timed rollout's own launches in a rocprofv3 kernel trace of `bench.py`.
+"""The timed rollout's own launches in a rocprofv3 kernel trace of `bench.py --full`.
 
-bench.py's dispatch order: GPU warm-up rollouts, the W warmup steps, the TIMED rollout, the stamped
+bench.py --full's dispatch order: GPU warm-up rollouts, the W warmup steps, the TIMED rollout, the stamped
 re-run of the timed rollout, then the launch-by-launch replay.  Every rollout call chain starts with
 one `gnca_ks_images` launch (the weight images), so the timed rollout is exactly the dispatches from
 the second-to-last `gnca_ks_images` up to (excluding) the last one.  Summarised per kernel: launches,
