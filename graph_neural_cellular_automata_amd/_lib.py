@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNCA_LIB_PATH: an alternative build of the same library (A/B measurement runs only)
 LIB_PATH = os.environ.get("GNCA_LIB_PATH") or os.path.join(_HERE, "libgnca.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 MAX_OFFSETS = 128
 
 GRAPH = 1 << 0
@@ -58,6 +58,17 @@ class Grads(ctypes.Structure):
         "w1", "b1", "w2", "gn_weight", "gn_bias", "wq", "bq", "wk", "bk", "wm", "bm", "scaling")]
 
 
+class RolloutSched(ctypes.Structure):
+    """Mirror of gnca_rollout_sched (include/gnca.h): offsets / fire_rate / message_gain are HOST
+    arrays read during the call, nsteps / fire are device pointers."""
+    _fields_ = [("steps", ctypes.c_int32), ("full_steps", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("offsets", ctypes.c_void_p), ("fire_rate", ctypes.c_void_p),
+                ("message_gain", ctypes.c_void_p), ("nsteps", ctypes.c_void_p), ("fire", ctypes.c_void_p)]
+
+
+SCHED_RECOMPUTE = 1 << 0
+
+
 class DamageDesc(ctypes.Structure):
     """Mirror of gnca_damage_desc (include/gnca.h)."""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -73,7 +84,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_perceive_f32", "gnca_rollout_f32", "gnca_bwd_workspace_bytes", "gnca_step_bwd_f32",
            "gnca_fire_mask_u8", "gnca_step_masked_f32", "gnca_damage_f32", "gnca_loss_premult_f32",
            "gnca_loss_premult_bwd_f32", "gnca_k1_variant", "gnca_rollout_stamped_f32",
-           "gnca_rollout_ex_f32", "gnca_bb_variant")
+           "gnca_rollout_ex_f32", "gnca_bb_variant", "gnca_rollout_tape_bytes",
+           "gnca_rollout_fwd_workspace_bytes", "gnca_rollout_bwd_workspace_bytes",
+           "gnca_rollout_fwd_f32", "gnca_rollout_bwd_f32")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -149,6 +162,17 @@ def load(path: str = LIB_PATH):
     lib.gnca_step_masked_f32.restype = ctypes.c_int
     lib.gnca_step_masked_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights), vp, vp, vp,
                                          vp, vp, sz, vp]
+    for name in ("gnca_rollout_tape_bytes", "gnca_rollout_fwd_workspace_bytes",
+                 "gnca_rollout_bwd_workspace_bytes"):
+        getattr(lib, name).restype = sz
+        getattr(lib, name).argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(RolloutSched)]
+    lib.gnca_rollout_fwd_f32.restype = ctypes.c_int
+    lib.gnca_rollout_fwd_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                         ctypes.POINTER(RolloutSched), vp, vp, vp, sz, vp, sz, vp]
+    lib.gnca_rollout_bwd_f32.restype = ctypes.c_int
+    lib.gnca_rollout_bwd_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                         ctypes.POINTER(RolloutSched), vp, sz, vp, vp,
+                                         ctypes.POINTER(Grads), vp, sz, vp]
     v = lib.gnca_abi_version()
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")

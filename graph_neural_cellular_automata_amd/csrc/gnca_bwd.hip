@@ -39,6 +39,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 
 #include "gnca_device.h"
 
@@ -110,6 +111,8 @@ struct BAArgs {
   int B, C, H, W, tps, band, nbands;
   float gain, thr, eps;
   int use_gn;
+  int acc;   // whole-rollout backward: the norm-gradient columns accumulate across steps (the two statistics
+             // columns, which BS consumes in the same step, are always overwritten)
 };
 
 __global__ __launch_bounds__(kThreads) void gnca_b_gnprep(const BAArgs a) {
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void gnca_b_gnprep(const BAArgs a) {
       a.gx[p] = a.gy[p];
       a.U[p] = 0.f;
     }
-    if (tid < 2 + 2 * C) a.part[(size_t)blockIdx.x * (2 + 2 * C) + tid] = 0.0;
+    if (tid < (a.acc ? 2 : 2 + 2 * C)) a.part[(size_t)blockIdx.x * (2 + 2 * C) + tid] = 0.0;
     return;
   }
   const int lane = tid & 63, wave = tid >> 6;
@@ -269,6 +272,10 @@ __global__ __launch_bounds__(kThreads) void gnca_b_gnprep(const BAArgs a) {
       x2 += __shfl_xor(x2, off);
     }
     if (lane == 0) {
+      if (a.acc) {
+        x2 += outp[2 + 2 * c];
+        x1 += outp[3 + 2 * c];
+      }
       outp[2 + 2 * c] = x2;
       outp[3 + 2 * c] = x1;
     }
@@ -402,8 +409,11 @@ struct BBArgs {
 #define GNCA_BB_W1SKEW 1      // the lean instances skew the W1 image's rows by 4 (lane >> 4) floats (A/B: 0)
 #endif
 // LL: the lean LDS layout (bb_layout's `lean`) of the large-tile instances
+// ACC: the wave's partial row is read, added to and written back (the whole-rollout backward, whose
+// rows are zeroed once and reduced once per rollout).  A template parameter, not a flag: the
+// instances without it are the same code, register for register, as before the mode existed
 template <int CP, int HB, bool FULL = false, int TH_ = 0, int TW_ = 0, int RY_ = 0, int RX_ = 0, int K_ = -1,
-          bool LL = false>
+          bool LL = false, bool ACC = false>
 __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int CPQ = CP / 4, KS = 3 * CPQ, MT = HB / 16, MO = (CP + 15) / 16, FT = (3 * CP + 15) / 16;
@@ -1077,6 +1087,14 @@ __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
   //      combine of the 4 waves into one row per workgroup measured slower: 131 vs 106 us per
   //      B=16 40x40 backward.) ----
   float* outp = a.part + ((size_t)blockIdx.x * NW + wave) * a.npart;
+  // ACC: the row carries the sum of the rollout's later steps (this wave alone owns it, and steps
+  // arrive in stream order: a fixed order of additions).  (Combining the 4 waves in LDS into one row
+  // per workgroup, the waves taking turns, moved a quarter of the bytes and measured slower: the
+  // B=128 72^2 80-step backward 20.3 vs 18.1 ms.)
+  auto put = [&](size_t i, float v) {
+    if constexpr (ACC) v += outp[i];
+    outp[i] = v;
+  };
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -1085,7 +1103,7 @@ __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
       for (int r = 0; r < 4; ++r) {
         const int hid = h0 + 16 * m + 4 * g + r, slot = 16 * ft + c16;
         const int f = slot / CP, c = slot - f * CP;
-        if (hid < Hd && slot < 3 * CP && c < C) outp[a.o_w1 + (size_t)hid * 3 * C + f * C + c] = aw1[m][ft][r];
+        if (hid < Hd && slot < 3 * CP && c < C) put(a.o_w1 + (size_t)hid * 3 * C + f * C + c, aw1[m][ft][r]);
       }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
@@ -1093,7 +1111,7 @@ __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
     v += __shfl_xor(v, 16);
     v += __shfl_xor(v, 32);
     const int hid = h0 + 16 * m + c16;
-    if (g == 0 && hid < Hd) outp[a.o_b1 + hid] = v;
+    if (g == 0 && hid < Hd) put(a.o_b1 + hid, v);
   }
 #pragma unroll
   for (int mo = 0; mo < MO; ++mo)
@@ -1102,9 +1120,10 @@ __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int c = 16 * mo + 4 * g + r, hid = h0 + 16 * m + c16;
-        if (c < C && hid < Hd) outp[a.o_w2 + (size_t)c * Hd + hid] = aw2[mo][m][r];
+        if (c < C && hid < Hd) put(a.o_w2 + (size_t)c * Hd + hid, aw2[mo][m][r]);
       }
-  if (first) {
+  // (an accumulating message-off step leaves the wm / bm columns alone: its sums are zeros)
+  if (ACC ? msg_bwd : first) {
 #pragma unroll
     for (int mo = 0; mo < MO; ++mo) {
 #pragma unroll
@@ -1112,14 +1131,14 @@ __global__ __launch_bounds__(kThreads, 1) void gnca_b_mlp(const BBArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int co = 16 * mo + 4 * g + r, ci = 16 * mi + c16;
-          if (co < C && ci < C) outp[a.o_wm + co * C + ci] = awm[mo][mi][r];
+          if (co < C && ci < C) put(a.o_wm + co * C + ci, awm[mo][mi][r]);
         }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float v = abm[mo][r];
         for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
         const int co = 16 * mo + 4 * g + r;
-        if (c16 == 0 && co < C) outp[a.o_bm + co] = v;
+        if (c16 == 0 && co < C) put(a.o_bm + co, v);
       }
     }
   }
@@ -1504,6 +1523,7 @@ struct BDArgs {
   double* pq;           // [B][2*d*C + 2*d + 1]
   float* corr;          // [B][H][C]
   int B, C, H, W, d, k, nrb;
+  int acc;              // whole-rollout backward: the sample's pq row accumulates across steps
   int8_t offs[2 * GNCA_MAX_OFFSETS];
 };
 
@@ -1614,24 +1634,25 @@ __global__ __launch_bounds__(kThreads) void gnca_b_attn(const BDArgs a) {
     gks[e] = s;
   }
   double* out = a.pq + (size_t)b * (2 * d * C + 2 * d + 1);
+  auto put = [&](int i, double v) { out[i] = a.acc ? out[i] + v : v; };   // (each element has one writer thread)
   for (int e = tid; e < d * C; e += kThreads) {
     const int j = e / C, c = e - j * C;
-    out[e] = gqp[j] * xbar[c];                       // dW_Q
+    put(e, gqp[j] * xbar[c]);                        // dW_Q
     double s = 0.0;
     for (int o = 0; o < k; ++o) s += gkp[o * d + j] * So[o * C + c];
-    out[d * C + d + e] = s / (double)HW;             // dW_K
+    put(d * C + d + e, s / (double)HW);              // dW_K
   }
   for (int j = tid; j < d; j += kThreads) {
-    out[d * C + j] = gqp[j];                         // db_Q
+    put(d * C + j, gqp[j]);                          // db_Q
     double s = 0.0;
     for (int o = 0; o < k; ++o) {
       const int dy = a.offs[2 * o];
       const int lo = dy > 0 ? 0 : -dy, hi = dy > 0 ? H - dy : H;
       s += gkp[o * d + j] * (double)(hi > lo ? hi - lo : 0) * (double)W;
     }
-    out[2 * d * C + d + j] = s / (double)HW;         // db_K
+    put(2 * d * C + d + j, s / (double)HW);          // db_K
   }
-  if (tid == 0) out[2 * d * C + 2 * d] = sc[0];      // d scaling
+  if (tid == 0) put(2 * d * C + 2 * d, sc[0]);       // d scaling
   __syncthreads();
   for (int e = tid; e < H * C; e += kThreads) {
     const int r = e / C, c = e - r * C;
@@ -1738,9 +1759,13 @@ struct BBVariant {
   int CP, HB;
   const void* fn;
   const void* fnf;   // the C == CP instance (16 and 32 channels), or null
+  const void* fna;   // their accumulating twins (ACC)
+  const void* fnfa;
 };
 #define GNCA_BV(cp, hb) {cp, hb, reinterpret_cast<const void*>(&gnca_b_mlp<cp, hb>), \
-                         (cp == 16 || cp == 32) ? reinterpret_cast<const void*>(&gnca_b_mlp<cp, hb, true>) : nullptr}
+                         (cp == 16 || cp == 32) ? reinterpret_cast<const void*>(&gnca_b_mlp<cp, hb, true>) : nullptr, \
+                         reinterpret_cast<const void*>(&gnca_b_mlp<cp, hb, false, 0, 0, 0, 0, -1, false, true>), \
+                         (cp == 16 || cp == 32) ? reinterpret_cast<const void*>(&gnca_b_mlp<cp, hb, true, 0, 0, 0, 0, -1, false, true>) : nullptr}
 static const BBVariant kBB[] = {
     GNCA_BV(16, 128), GNCA_BV(4, 32),  GNCA_BV(8, 32),  GNCA_BV(16, 32), GNCA_BV(4, 64),
     GNCA_BV(8, 64),   GNCA_BV(12, 64), GNCA_BV(16, 64), GNCA_BV(20, 64), GNCA_BV(24, 64),
@@ -1756,14 +1781,27 @@ struct BBSpec {
   int TH, TW, RY, RX, K;
   bool lean;
   const void* fn;
+  const void* fna;   // the accumulating twin (ACC)
 };
 #define GNCA_BS(th, tw, ry, rx, k, ll) \
-  {th, tw, ry, rx, k, ll, reinterpret_cast<const void*>(&gnca_b_mlp<16, 128, true, th, tw, ry, rx, k, ll>)}
+  {th, tw, ry, rx, k, ll, reinterpret_cast<const void*>(&gnca_b_mlp<16, 128, true, th, tw, ry, rx, k, ll>), \
+   reinterpret_cast<const void*>(&gnca_b_mlp<16, 128, true, th, tw, ry, rx, k, ll, true>)}
 static const BBSpec kBBS[] = {
     GNCA_BS(8, 24, 4, 4, 8, false), GNCA_BS(8, 16, 4, 4, 8, false), GNCA_BS(8, 24, 1, 4, 0, false),
     GNCA_BS(8, 16, 1, 4, 0, false), GNCA_BS(24, 24, 4, 4, 8, true), GNCA_BS(24, 24, 1, 4, 0, true),
 };
 #undef GNCA_BS
+
+// the accumulating twin of a planned BB kernel
+static const void* bb_acc_fn(const void* fn) {
+  for (const BBSpec& sp : kBBS)
+    if (sp.fn == fn) return sp.fna;
+  for (const BBVariant& v : kBB) {
+    if (v.fn == fn) return v.fna;
+    if (v.fnf && v.fnf == fn) return v.fnfa;
+  }
+  return nullptr;
+}
 
 struct BwdPlan {
   FwdLayout F;
@@ -2107,13 +2145,26 @@ int gnca_bb_variant(const gnca_step_desc* desc, char* name, int32_t n) {
   return GNCA_OK;
 }
 
-int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x,
-                      const void* fire, const uint8_t* active, const float* gy, float* gx,
-                      const gnca_grads* grads, const void* saved, void* ws, size_t ws_bytes,
-                      void* stream) {
+}  // extern "C"
+
+// The whole-rollout backward's accumulating partial rows (null in gnca_step_bwd_f32: the step's own
+// rows in its workspace, reduced by the step).  With them, BB / BA / BD add this step's partials to
+// the rows and the step launches no reduction and forks no side stream: gnca_rollout_bwd_f32 zeroes
+// the rows before its first step and reduces them after its last.
+struct BwdAccum {
+  float* pb;    // [max BB grid * NW][npart]
+  double* pa;   // [B * nbands][2 + 2C] (columns 0, 1: per-step statistics, overwritten)
+  double* pq;   // [B][nq] (zero-pad attention), or null
+};
+
+// One step's vector-Jacobian product: the body of gnca_step_bwd_f32 (acc == nullptr: exactly its
+// launches) and of every step of gnca_rollout_bwd_f32 (acc != nullptr; grads is not used).
+static int step_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, const float* x,
+                         const void* fire, const uint8_t* active, const float* gy, float* gx,
+                         const gnca_grads* grads, const void* saved, void* ws, size_t ws_bytes,
+                         void* stream, const BwdAccum* acc) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  StreamDeviceGuard dg(st);
-  if (!desc || !w || !x || !gy || !gx || !grads) return GNCA_ERR_INVALID;
+  if (!desc || !w || !x || !gy || !gx || (!grads && !acc)) return GNCA_ERR_INVALID;
   if (gx == x || gx == gy) return GNCA_ERR_INVALID;
   gnca_step_desc d = *desc;
   d.flags &= ~GNCA_ATTENTION;
@@ -2151,9 +2202,9 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
 #else
   uint8_t* keep = nullptr;
 #endif
-  double* pa = reinterpret_cast<double*>(wsb + P.off_pa);
+  double* pa = acc ? acc->pa : reinterpret_cast<double*>(wsb + P.off_pa);
   float* coef = reinterpret_cast<float*>(wsb + P.off_coef);
-  float* pb = reinterpret_cast<float*>(wsb + P.off_pb);
+  float* pb = acc ? acc->pb : reinterpret_cast<float*>(wsb + P.off_pb);
   // BA
   {
     BAArgs a;
@@ -2162,6 +2213,7 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
     a.gx = gx; a.U = U; a.part = pa; a.active = active;
     a.B = B; a.C = C; a.H = H; a.W = W; a.tps = P.F.tps; a.band = P.band; a.nbands = P.nbands;
     a.gain = d.update_gain; a.thr = d.alpha_thr; a.eps = d.gn_eps; a.use_gn = P.gn ? 1 : 0;
+    a.acc = acc ? 1 : 0;
     hipLaunchKernelGGL(gnca_b_gnprep, dim3(B * P.nbands), dim3(kThreads), P.ldsA, st, a);
     if ((rc = bwd_check()) != GNCA_OK) return rc;
   }
@@ -2216,22 +2268,26 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
 #ifndef GNCA_BB_NO_DMA4   // A/B builds: 4-byte staging pieces (round 4's BB)
     if (W % 4 == 0 && P.RXB % 4 == 0 && P.TW % 4 == 0 && P.bbf32) a.flags |= kDma4;
 #endif
-    (void)hipFuncSetAttribute(P.bbfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsB);
-    (void)hipFuncSetAttribute(P.bbfn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsB);
+    const void* bbfn = acc ? bb_acc_fn(P.bbfn) : P.bbfn;
+    const void* bbfn2 = acc ? bb_acc_fn(P.bbfn2) : P.bbfn2;
+    if (!bbfn || !bbfn2) return GNCA_ERR_INVALID;
+    (void)hipFuncSetAttribute(bbfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsB);
+    (void)hipFuncSetAttribute(bbfn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsB);
     for (int s = 0; s < P.nslices; ++s) {
       a.h0 = s * P.HB;
       a.flags = (a.flags & ~kFirst) | (s == 0 ? kFirst : 0u);
       void* args[] = {&a};
-      const hipError_t e = hipLaunchKernel(s == 0 ? P.bbfn : P.bbfn2, dim3(P.gridB), dim3(kThreads), args, P.ldsB, st);
+      const hipError_t e = hipLaunchKernel(s == 0 ? bbfn : bbfn2, dim3(P.gridB), dim3(kThreads), args, P.ldsB, st);
       if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
       if ((rc = bwd_check()) != GNCA_OK) return rc;
     }
   }
   // the weight-gradient reductions (BB's and BA's partial rows) on the side stream, beside BC
-  SideFork sf(st, (long)B * (long)HW);
+  // (accumulating rows: no reduction in the step, so no fork either)
+  SideFork sf(st, acc ? 0 : (long)B * (long)HW);
   if (!sf.ok) return GNCA_ERR_HIP;
   const int dmod = std::max(d.d_model, 1);
-  {
+  if (!acc) {
     Reducer r(pb, false, (long)P.gridB * NW, P.npart);
     r.add(P.o_w1, Hd * 3 * C, 1, grads->w1);
     r.add(P.o_b1, Hd, 1, grads->b1);
@@ -2249,7 +2305,7 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
     }
     if ((rc = r.launch(sf.side)) != GNCA_OK) return rc;
   }
-  if (P.gn) {
+  if (P.gn && !acc) {
     Reducer r(pa, true, (long)B * P.nbands, 2 + 2 * C);
     r.add(2, C, 2, grads->gn_weight);
     r.add(3, C, 2, grads->gn_bias);
@@ -2283,7 +2339,8 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
   }
   if (!P.graph || !(P.msg && P.zp)) return GNCA_OK;
   double* dots = reinterpret_cast<double*>(wsb + P.off_dots);
-  double* pq = reinterpret_cast<double*>(wsb + P.off_pq);
+  double* pq = acc ? acc->pq : reinterpret_cast<double*>(wsb + P.off_pq);
+  if (!pq) return GNCA_ERR_INVALID;
   float* corr = reinterpret_cast<float*>(wsb + P.off_corr);
   {
     BC2Args a;
@@ -2304,6 +2361,7 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
     a.rs = reinterpret_cast<const double*>(fw + P.F.off_rs);
     a.dots = dots; a.pq = pq; a.corr = corr;
     a.B = B; a.C = C; a.H = H; a.W = W; a.d = d.d_model; a.k = P.F.k; a.nrb = P.nrb;
+    a.acc = acc ? 1 : 0;
     for (int o = 0; o < 2 * P.F.k; ++o) a.offs[o] = d.offsets[o];
     hipLaunchKernelGGL(gnca_b_attn, dim3(B), dim3(kThreads), P.ldsD, st, a);
     if ((rc = bwd_check()) != GNCA_OK) return rc;
@@ -2316,9 +2374,179 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
                        B, C, H, W);
     if ((rc = bwd_check()) != GNCA_OK) return rc;
   }
-  {
+  if (!acc) {
     const int dq = d.d_model;
     Reducer r(pq, true, B, P.nq);
+    r.add(0, dq * C, 1, grads->wq);
+    r.add(dq * C, dq, 1, grads->bq);
+    r.add(dq * C + dq, dq * C, 1, grads->wk);
+    r.add(2 * dq * C + dq, dq, 1, grads->bk);
+    r.add(2 * dq * C + 2 * dq, 1, 1, grads->scaling);
+    if ((rc = r.launch(st)) != GNCA_OK) return rc;
+  }
+  return GNCA_OK;
+}
+
+// Workspace of the whole-rollout backward:
+//   [active masks | two gradient states (ping-pong) | BB rows | BA rows | BD rows | one step's workspace]
+// The BB row block is sized for the largest grid any step of the schedule plans (message-on and
+// message-off steps, masked and full steps plan different BB instances and grids; the column layout
+// depends on C and the hidden width alone, so one block serves them all) and that many rows are reduced:
+// the rows a smaller grid leaves alone stay zero.
+struct RollBwdLayout {
+  TapeLayout T;
+  size_t off_g[2], off_pb, off_pa, off_pq, off_step, step_bytes, pb_bytes, pa_bytes, pq_bytes, bytes;
+  long pb_rows;
+  int npart, nbands, nq;
+  int o_w1, o_b1, o_w2, o_wm, o_bm;
+  bool gn, graph, att;
+};
+
+static bool roll_bwd_layout(const gnca_step_desc* desc, const gnca_rollout_sched* s, RollBwdLayout* R) {
+  if (!tape_layout(desc, s, &R->T)) return false;
+  gnca_step_desc d0 = *desc;
+  d0.flags &= ~GNCA_ATTENTION;
+  BwdPlan P;
+  if (!bwd_plan(&d0, &P)) return false;
+  R->npart = P.npart; R->nbands = P.nbands; R->nq = P.nq;
+  R->o_w1 = P.o_w1; R->o_b1 = P.o_b1; R->o_w2 = P.o_w2; R->o_wm = P.o_wm; R->o_bm = P.o_bm;
+  R->gn = P.gn; R->graph = P.graph;
+  R->att = P.graph && P.zp && P.F.k > 0;
+  size_t step_bytes = 0;
+  long rows = 0;
+  auto take = [&](const gnca_step_desc* d) {
+    for (int lean = 0; lean < 2; ++lean) {
+      BwdPlan Q;
+      if (!bwd_plan(d, &Q, lean != 0)) return false;
+      step_bytes = std::max(step_bytes, Q.bytes);
+      rows = std::max(rows, (long)Q.gridB * NW);
+    }
+    return true;
+  };
+  if (!take(&d0)) return false;
+  std::vector<uint32_t> seen;
+  for (int t = 0; t < s->steps; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, s, t, &sd);
+    int ry = 0, rx = 0;
+    for (int o = 0; o < sd.num_offsets; ++o) {
+      ry = std::max(ry, std::abs((int)sd.offsets[2 * o]));
+      rx = std::max(rx, std::abs((int)sd.offsets[2 * o + 1]));
+    }
+    const uint32_t key = (sd.message_gain != 0.f ? 1u << 16 : 0u) | ((uint32_t)ry << 8) | (uint32_t)rx;
+    if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
+    seen.push_back(key);
+    if (!take(&sd)) return false;
+  }
+  R->pb_rows = rows;
+  R->step_bytes = align256(step_bytes);
+  R->pb_bytes = align256((size_t)rows * R->npart * sizeof(float));
+  R->pa_bytes = align256((size_t)desc->B * R->nbands * (2 + 2 * desc->C) * sizeof(double));
+  R->pq_bytes = R->att ? align256((size_t)desc->B * R->nq * sizeof(double)) : 0;
+  size_t o = R->T.masks;
+  R->off_g[0] = o; o += R->T.state;
+  R->off_g[1] = o; o += R->T.state;
+  R->off_pb = o; o += R->pb_bytes;
+  R->off_pa = o; o += R->pa_bytes;
+  R->off_pq = o; o += R->pq_bytes;
+  R->off_step = o; o += R->step_bytes;
+  R->bytes = o;
+  return true;
+}
+
+extern "C" {
+
+int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x,
+                      const void* fire, const uint8_t* active, const float* gy, float* gx,
+                      const gnca_grads* grads, const void* saved, void* ws, size_t ws_bytes,
+                      void* stream) {
+  StreamDeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
+  if (!grads) return GNCA_ERR_INVALID;
+  return step_bwd_impl(desc, w, x, fire, active, gy, gx, grads, saved, ws, ws_bytes, stream, nullptr);
+}
+
+size_t gnca_rollout_bwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched) {
+  RollBwdLayout R;
+  return roll_bwd_layout(desc, sched, &R) ? R.bytes : 0;
+}
+
+int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const void* tape, size_t tape_bytes, const float* gy, float* gx,
+                         const gnca_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  if (!desc || !w || !sched || !gy || !gx || gx == gy) return GNCA_ERR_INVALID;
+  RollBwdLayout R;
+  if (!roll_bwd_layout(desc, sched, &R)) return GNCA_ERR_INVALID;
+  const int T = sched->steps;
+  if (T > 0 && (!tape || tape_bytes < R.T.bytes)) return tape ? GNCA_ERR_WORKSPACE : GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && T > 0 && !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  char* wsb = reinterpret_cast<char*>(ws);
+  const char* tp = reinterpret_cast<const char*>(tape);
+  const int B = desc->B, C = desc->C, Hd = desc->hidden;
+  const size_t nbytes = (size_t)B * C * desc->H * desc->W * sizeof(float);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  float* gb[2] = {reinterpret_cast<float*>(wsb + R.off_g[0]), reinterpret_cast<float*>(wsb + R.off_g[1])};
+  BwdAccum acc;
+  acc.pb = reinterpret_cast<float*>(wsb + R.off_pb);
+  acc.pa = reinterpret_cast<double*>(wsb + R.off_pa);
+  acc.pq = R.att ? reinterpret_cast<double*>(wsb + R.off_pq) : nullptr;
+  int rc;
+  // the rows start at zero, once per rollout
+  if (hipMemsetAsync(acc.pb, 0, R.pb_bytes, st) != hipSuccess || hipMemsetAsync(acc.pa, 0, R.pa_bytes, st) != hipSuccess ||
+      (acc.pq && hipMemsetAsync(acc.pq, 0, R.pq_bytes, st) != hipSuccess))
+    return GNCA_ERR_HIP;
+  if (T == 0) {
+    if (hipMemcpyAsync(gx, gy, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
+  } else if (sched->nsteps &&
+             (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK) {
+    return rc;
+  }
+  const bool recompute = (sched->flags & GNCA_SCHED_RECOMPUTE) != 0;
+  const float* g = gy;
+  for (int t = T - 1; t >= 0; --t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    const float* xt = reinterpret_cast<const float*>(tp + (size_t)t * R.T.slot);
+    const void* saved = recompute ? nullptr : static_cast<const void*>(tp + (size_t)t * R.T.slot + R.T.state);
+    float* out = t == 0 ? gx : gb[t & 1];
+    rc = step_bwd_impl(&sd, w, xt, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), g, out,
+                       nullptr, saved, wsb + R.off_step, R.step_bytes, stream, &acc);
+    if (rc != GNCA_OK) return rc;
+    g = out;
+  }
+  if (!grads) return GNCA_OK;
+  // one reduction of each row block per rollout
+  {
+    Reducer r(acc.pb, false, R.pb_rows, R.npart);
+    r.add(R.o_w1, Hd * 3 * C, 1, grads->w1);
+    r.add(R.o_b1, Hd, 1, grads->b1);
+    r.add(R.o_w2, C * Hd, 1, grads->w2);
+    if (R.graph) {
+      r.add(R.o_wm, C * C, 1, grads->wm);
+      r.add(R.o_bm, C, 1, grads->bm);
+      if (!R.att) {   // torus (or no offsets): the offset weights are constants
+        const int dmod = std::max(desc->d_model, 1);
+        r.add(0, dmod * C, 0, grads->wq);
+        r.add(0, dmod, 0, grads->bq);
+        r.add(0, dmod * C, 0, grads->wk);
+        r.add(0, dmod, 0, grads->bk);
+        r.add(0, 1, 0, grads->scaling);
+      }
+    }
+    if ((rc = r.launch(st)) != GNCA_OK) return rc;
+  }
+  if (R.gn) {
+    Reducer r(acc.pa, true, (long)B * R.nbands, 2 + 2 * C);
+    r.add(2, C, 2, grads->gn_weight);
+    r.add(3, C, 2, grads->gn_bias);
+    if ((rc = r.launch(st)) != GNCA_OK) return rc;
+  }
+  if (R.att) {
+    const int dq = desc->d_model;
+    Reducer r(acc.pq, true, B, R.nq);
     r.add(0, dq * C, 1, grads->wq);
     r.add(dq * C, dq, 1, grads->bq);
     r.add(dq * C + dq, dq * C, 1, grads->wk);

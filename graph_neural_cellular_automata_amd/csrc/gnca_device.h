@@ -292,6 +292,56 @@ int gnca_step_masked_phases(const gnca_step_desc* d, const gnca_weights* w, cons
                             const void* fire, const uint8_t* active, void* ws, size_t ws_bytes,
                             void* stream, uint32_t phases);
 
+// ---------------------------------------------------------------------------------------------
+// Whole-rollout schedule (gnca_rollout_fwd_f32 / gnca_rollout_bwd_f32), shared by both directions
+// ---------------------------------------------------------------------------------------------
+inline bool sched_ok(const gnca_step_desc* d, const gnca_rollout_sched* s) {
+  if (!d || !s || s->steps < 0 || s->full_steps < 0) return false;
+  if (d->num_offsets < 0 || d->num_offsets > GNCA_MAX_OFFSETS) return false;
+  if ((d->flags & GNCA_GRAPH) && d->num_offsets > 0 && s->steps > 0 && !s->offsets) return false;
+  return true;
+}
+
+// step t's descriptor: the schedule's offsets, fire rate and message gain, rng_step + t
+inline void sched_step_desc(const gnca_step_desc* d, const gnca_rollout_sched* s, int t, gnca_step_desc* o) {
+  *o = *d;
+  o->flags &= ~GNCA_ATTENTION;
+  const int k2 = 2 * d->num_offsets;
+  if (s->offsets && (d->flags & GNCA_GRAPH))
+    for (int i = 0; i < k2; ++i) o->offsets[i] = s->offsets[(size_t)t * k2 + i];
+  if (s->fire_rate) o->fire_rate = s->fire_rate[t];
+  if (s->message_gain) o->message_gain = s->message_gain[t];
+  o->rng_step = d->rng_step + t;
+}
+
+// step t's fire input ([B,1,H,W] uniforms or mask bytes of the [T] stack), or null
+inline const void* sched_step_fire(const gnca_step_desc* d, const gnca_rollout_sched* s, int t) {
+  if (!s->fire) return nullptr;
+  const size_t cells = (size_t)d->B * d->H * d->W;
+  if (d->fire_mode == GNCA_FIRE_RAND_F32) return reinterpret_cast<const float*>(s->fire) + (size_t)t * cells;
+  if (d->fire_mode == GNCA_FIRE_MASK_U8) return reinterpret_cast<const uint8_t*>(s->fire) + (size_t)t * cells;
+  return nullptr;
+}
+
+// step t's active-sample mask in the [T][B] mask block (null: every sample runs)
+inline const uint8_t* sched_step_active(const gnca_step_desc* d, const gnca_rollout_sched* s, int t,
+                                        const uint8_t* masks) {
+  return (s->nsteps && t >= s->full_steps) ? masks + (size_t)t * d->B : nullptr;
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The tape: slot t = [state S_t | the step's forward workspace (absent with GNCA_SCHED_RECOMPUTE)].
+// fwd_ws: the largest forward workspace of the schedule's steps (plans differ between message-on
+// and message-off steps and with the offsets' reach).
+struct TapeLayout {
+  size_t state, fwd_ws, slot, bytes, masks;
+};
+bool tape_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, TapeLayout* out);
+
+// masks[t][b] = t < full_steps || t < nsteps[b] (uint8 [T][B]), one launch
+int launch_nsteps_masks(const int32_t* nsteps, int B, int T, int full_steps, uint8_t* masks, hipStream_t st);
+
 // hipError_t of the last failed launch on this thread (gnca_last_hip_error)
 extern thread_local int g_last_hip;
 

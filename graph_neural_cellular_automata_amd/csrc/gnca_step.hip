@@ -35,6 +35,7 @@
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
+#include <vector>
 
 #include "gnca_device.h"
 
@@ -2709,6 +2710,122 @@ int gnca_rollout_stamped_f32(const gnca_step_desc* desc, const gnca_weights* w, 
   if (!stamps || stamp_cap <= 0) return GNCA_ERR_INVALID;
   return rollout_impl(desc, w, steps, offsets, x, x_final, scratch, ws, ws_bytes, stream, stamps,
                       stamp_cap, 0u);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Whole-rollout forward on a schedule, with a tape for gnca_rollout_bwd_f32
+// ---------------------------------------------------------------------------------------------
+namespace gnca {
+
+// one thread per (t, b)
+__global__ __launch_bounds__(kThreads) void gnca_k_nsteps_masks(const int32_t* nsteps, int B, int T, int full_steps,
+                                                                uint8_t* masks) {
+  const long e = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= (long)T * B) return;
+  const int t = (int)(e / B), b = (int)(e - (long)t * B);
+  masks[e] = (t < full_steps || t < nsteps[b]) ? 1 : 0;
+}
+
+int launch_nsteps_masks(const int32_t* nsteps, int B, int T, int full_steps, uint8_t* masks, hipStream_t st) {
+  const long n = (long)T * B;
+  if (n <= 0) return GNCA_OK;
+  hipLaunchKernelGGL(gnca_k_nsteps_masks, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     nsteps, B, T, full_steps, masks);
+  return check_launch();
+}
+
+// The plan (hence the workspace size) of a step depends on whether its message is on and on how far
+// its offsets reach, nothing else the schedule varies: one make_plan per distinct combination.
+bool tape_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, TapeLayout* out) {
+  if (!sched_ok(d, s)) return false;
+  Plan P;
+  if (!make_plan(d, false, &P)) return false;
+  size_t m = P.ws_bytes;
+  std::vector<uint32_t> seen;
+  for (int t = 0; t < s->steps; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(d, s, t, &sd);
+    int ry = 0, rx = 0;
+    for (int o = 0; o < sd.num_offsets; ++o) {
+      ry = std::max(ry, std::abs((int)sd.offsets[2 * o]));
+      rx = std::max(rx, std::abs((int)sd.offsets[2 * o + 1]));
+    }
+    const uint32_t key = (sd.message_gain != 0.f ? 1u << 16 : 0u) | ((uint32_t)ry << 8) | (uint32_t)rx;
+    if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
+    seen.push_back(key);
+    if (!make_plan(&sd, false, &P)) return false;
+    m = std::max(m, P.ws_bytes);
+  }
+  out->state = align256((size_t)d->B * d->C * d->H * d->W * sizeof(float));
+  out->fwd_ws = align256(m);
+  out->slot = out->state + ((s->flags & GNCA_SCHED_RECOMPUTE) ? 0 : out->fwd_ws);
+  out->bytes = (size_t)s->steps * out->slot;
+  out->masks = align256((size_t)std::max(s->steps, 1) * d->B);
+  return true;
+}
+
+}  // namespace gnca
+
+extern "C" {
+
+size_t gnca_rollout_tape_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched) {
+  TapeLayout L;
+  return tape_layout(desc, sched, &L) ? L.bytes : 0;
+}
+
+// [masks | one step workspace | two states (the no-tape form)]
+size_t gnca_rollout_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched) {
+  TapeLayout L;
+  return tape_layout(desc, sched, &L) ? L.masks + L.fwd_ws + 2 * L.state : 0;
+}
+
+int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const float* x, float* x_final, void* tape, size_t tape_bytes, void* ws,
+                         size_t ws_bytes, void* stream) {
+  if (!desc || !w || !sched || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
+  TapeLayout L;
+  if (!tape_layout(desc, sched, &L)) return GNCA_ERR_INVALID;
+  if (tape && tape_bytes < L.bytes) return GNCA_ERR_WORKSPACE;
+  if (!ws || ws_bytes < L.masks + L.fwd_ws + 2 * L.state) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && sched->steps > 0 &&
+      !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  const int T = sched->steps;
+  const size_t nbytes = (size_t)desc->B * desc->C * desc->H * desc->W * sizeof(float);
+  char* wsb = reinterpret_cast<char*>(ws);
+  char* tp = reinterpret_cast<char*>(tape);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + L.masks;
+  float* pp[2] = {reinterpret_cast<float*>(wsb + L.masks + L.fwd_ws),
+                  reinterpret_cast<float*>(wsb + L.masks + L.fwd_ws + L.state)};
+  int rc;
+  if (T == 0) {
+    if (hipMemcpyAsync(x_final, x, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
+    return GNCA_OK;
+  }
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, desc->B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  const bool slot_ws = tape && !(sched->flags & GNCA_SCHED_RECOMPUTE);
+  const float* cur = x;
+  if (tape) {   // the tape stands alone: slot 0 keeps its own copy of x
+    if (hipMemcpyAsync(tp, x, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
+    cur = reinterpret_cast<const float*>(tp);
+  }
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* nxt = t == T - 1 ? x_final : tape ? reinterpret_cast<float*>(tp + (size_t)(t + 1) * L.slot) : pp[t & 1];
+    void* sws = slot_ws ? static_cast<void*>(tp + (size_t)t * L.slot + L.state) : static_cast<void*>(step_ws);
+    rc = step_impl(&sd, w, cur, nxt, sched_step_fire(desc, sched, t), nullptr, sws, L.fwd_ws, st, GNCA_PHASE_ALL,
+                   sched_step_active(desc, sched, t, masks));
+    if (rc != GNCA_OK) return rc;
+    cur = nxt;
+  }
+  return GNCA_OK;
 }
 
 }  // extern "C"

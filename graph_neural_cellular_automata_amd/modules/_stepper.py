@@ -245,3 +245,98 @@ def run_step(model: nn.Module, x: torch.Tensor, fire_rate: float, graph, chosen,
     else:
         out, attn = S.step(desc, w, x, fire=fire, want_attention=return_attention, active=active)
     return out, attn
+
+
+class _RolloutFn(torch.autograd.Function):
+    """A whole rollout as ONE autograd node: ``gnca_rollout_fwd_f32`` with a tape forward,
+    ``gnca_rollout_bwd_f32`` backward.  The weight-gradient partials are accumulated across the
+    steps on the device and reduced once, so the parameter gradients leave as one flat tensor per
+    pack per rollout (``_ParamPack``), not one per step."""
+
+    @staticmethod
+    def forward(ctx, x, call, weights, keep, core, graph, tok_core, tok_graph, tensors=None):
+        out, tape = call.forward(weights, x, want_tape=True)
+        ctx.call, ctx.weights, ctx.keep, ctx.tape = call, weights, keep, tape
+        ctx.packs = (core, graph)
+        # raw weight pointers: check the versions ourselves, as _StepFn does
+        ctx.versions = tuple((t, t._version) for t in (tensors or {}).values())
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        for t, v in ctx.versions:
+            if t._version != v:
+                raise RuntimeError(
+                    "one of the variables needed for gradient computation has been modified by an "
+                    f"inplace operation: a rollout weight of shape {tuple(t.shape)} is at version "
+                    f"{t._version}; expected version {v} instead")
+        if ctx.tape is None:
+            raise RuntimeError("rollout: backward through the same rollout a second time (its tape was freed)")
+        desc = ctx.call.desc
+        no_graph_use = (desc.flags & L.GRAPH) and desc.num_offsets == 0
+        want, views, flats = {}, {}, [None, None]
+        for i, pack in enumerate(ctx.packs):
+            if pack is None or not ctx.needs_input_grad[6 + i] or (i == 1 and no_graph_use):
+                continue
+            flats[i] = torch.empty(sum(pack.sizes), dtype=torch.float32, device=gout.device)
+            views.update(pack.views(flats[i]))
+            want.update(zip(pack.names, pack.params))
+        gx, _ = ctx.call.backward(ctx.weights, ctx.tape, gout.contiguous(), want=want, out=views)
+        ctx.tape = None
+        return (gx if ctx.needs_input_grad[0] else None, None, None, None, None, None, flats[0], flats[1], None)
+
+
+def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
+                message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0, offsets=None,
+                recompute=False):
+    """``steps`` CA steps in one native call (and, with grad, one autograd node): the shared body of
+    ``NeuralCA.rollout`` / ``NeuralCAGraph.rollout``."""
+    x = S.check_state(x, model.n_channels)
+    B, C, H, W = x.shape
+    flags = 0
+    norm = model._modules["norm"]
+    eps = 1e-3
+    if isinstance(norm, nn.GroupNorm):
+        if norm.num_groups != 1 or not norm.affine:
+            raise ValueError("only GroupNorm(1, C, affine=True) is supported (ncagraph.py:68)")
+        flags |= L.USE_GROUPNORM
+        eps = norm.eps
+    elif not isinstance(norm, nn.Identity):
+        raise ValueError(f"unsupported norm module {type(norm).__name__}")
+    sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                             sample_base=sample_base, offsets=offsets,
+                             sample_offsets=None if graph is None else graph.sample_offsets, recompute=recompute)
+    tensors = _step_tensors(model, graph)
+    d_model = 1
+    graph_thr = None
+    if graph is not None:
+        flags |= graph.flags(False)
+        if hidden_only:
+            flags |= L.HIDDEN_ONLY
+        d_model = graph.d_model
+        graph_thr = graph.alpha_thr
+    alpha_thr = float(model.alpha_thr)
+    key = (B, C, H, W, tensors["w1"].shape[0], d_model, flags, float(model.update_gain), alpha_thr,
+           alpha_thr if graph_thr is None else float(graph_thr), float(eps))
+    first = sched.offsets[0] if sched.offsets and steps > 0 else None
+    desc = _step_desc(key, first, sched.gains[0] if sched.gains and steps > 0 else 0.0,
+                      sched.fire_rates[0] if steps > 0 else 1.0, sched.fire_mode)
+    desc.num_offsets = sched.k
+    if steps == 0 and graph is not None:
+        # nothing was drawn: keep the count forward() would draw, so that the (all-zero) graph
+        # gradients are tensors, as after a rollout of message-off steps
+        desc.num_offsets = min(graph.num_neighbors, len(graph.offsets))
+    desc.rng_seed = sched.seed & 0xFFFFFFFFFFFFFFFF
+    desc.sample_base = sched.sample_base
+    w, keep = S.make_weights(tensors)
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors.values())):
+        core, gpack = param_packs(model, tensors)
+        tc = core.token if core is not None else None
+        tg = gpack.token if gpack is not None else None
+        return _RolloutFn.apply(x, S.RolloutCall(desc, sched), w, keep, core, gpack, tc, tg, tensors)
+    if sched.uniform and steps > 0:
+        # the no-grad pipeline (compact update field, sub-batch streams, the fold, alive hand-over)
+        return S.rollout(desc, w, x, steps, sched.offsets or [])
+    out, _ = S.RolloutCall(desc, sched).forward(w, x, want_tape=False)
+    return out

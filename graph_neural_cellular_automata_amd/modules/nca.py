@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import run_step
+from ._stepper import run_rollout, run_step
 from .perception import FixedSobelPerception
 
 
@@ -35,3 +35,10 @@ class NeuralCA(nn.Module):
         """One CA step on the HIP path (nca.py:64-105).  ``active``: see NeuralCAGraph.forward."""
         out, _ = run_step(self, x, fire_rate, None, None, 0.0, False, False, active=active)
         return out
+
+    def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
+                fire=None, seed=None, sample_base: int = 0, recompute: bool = False) -> torch.Tensor:
+        """``steps`` CA steps in one native call, one autograd node with grad enabled: see
+        ``NeuralCAGraph.rollout`` (no ``message_gain`` / ``offsets`` here)."""
+        return run_rollout(self, x, steps, None, False, fire_rate=fire_rate, nsteps=nsteps, min_steps=min_steps,
+                           fire=fire, seed=seed, sample_base=sample_base, recompute=recompute)

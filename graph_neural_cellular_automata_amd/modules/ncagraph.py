@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import run_step
+from ._stepper import run_rollout, run_step
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -69,3 +69,28 @@ class NeuralCAGraph(nn.Module):
         out, attn = run_step(self, x, fire_rate, self.graph, chosen, self.message_gain,
                              self.hidden_only, return_attention, active=active)
         return (out, attn) if return_attention else out
+
+    def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
+                min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,
+                recompute: bool = False) -> torch.Tensor:
+        """``steps`` CA steps in one native call (extension, not in the reference); with grad enabled
+        the whole rollout is ONE autograd node whose backward walks a device-side tape and reduces
+        the weight gradients once per rollout.
+
+        ``fire_rate`` / ``message_gain``: a number or ``steps`` numbers (``message_gain=None``:
+        ``self.message_gain``).  ``offsets=None`` draws ``self.graph.sample_offsets()`` once per step
+        in step order, consuming Python's ``random`` exactly as ``steps`` ``forward`` calls do
+        (message-off steps included); else ``steps`` lists of (dy, dx) pairs.  ``nsteps``: int32 [B]
+        device tensor, sample b takes step t iff ``t < nsteps[b]`` (the trainers' variable-length
+        rollouts, never read on the host); steps ``t < min_steps`` run every sample.  ``fire``: a
+        [steps,B,1,H,W] tensor of float32 uniforms or uint8 / bool masks; ``fire=None`` with a rate
+        below 1 uses the counter-based hash masks of ``seed`` (``seed=None`` draws one integer from
+        torch's default CPU generator) -- NOT the ``torch.rand`` stream ``forward`` draws from.
+        ``recompute=True`` halves the tape (the backward recomputes each step's update field).
+        Under ``no_grad`` a uniform schedule (one rate, one gain, no ``nsteps``, hash or no fire)
+        runs the large-batch rollout pipeline (``gnca_rollout_ex_f32``).  ``return_attention`` is
+        not supported here."""
+        return run_rollout(self, x, steps, self.graph, self.hidden_only, fire_rate=fire_rate,
+                           message_gain=self.message_gain if message_gain is None else message_gain,
+                           nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
+                           offsets=offsets, recompute=recompute)

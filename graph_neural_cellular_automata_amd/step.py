@@ -313,3 +313,189 @@ def step_backward(desc, weights, x, gy, fire=None, want: dict | None = None, sav
                                ws.data_ptr(), ws.numel(), stream_ptr(x.device))
     L.check(rc, "gnca_step_bwd_f32")
     return gx, out
+
+
+# ---------------------------------------------------------------------------------------------
+# Whole-rollout schedule (gnca_rollout_fwd_f32 / gnca_rollout_bwd_f32)
+# ---------------------------------------------------------------------------------------------
+class Schedule:
+    """A validated per-step schedule of one rollout (``build_schedule``): plain Python values and
+    the caller's device tensors; ``RolloutCall`` turns it into the C struct."""
+
+    __slots__ = ("steps", "full_steps", "recompute", "offsets", "k", "fire_rates", "gains", "nsteps",
+                 "fire", "fire_mode", "seed", "sample_base")
+
+    @property
+    def uniform(self) -> bool:
+        """One rate, one gain, every sample every step, hash or no fire: the schedule the no-grad
+        pipeline of ``gnca_rollout_ex_f32`` runs."""
+        return (self.nsteps is None and self.fire is None and len(set(self.fire_rates)) <= 1
+                and (self.gains is None or len(set(self.gains)) <= 1))
+
+
+def _per_step(value, steps: int, name: str) -> list:
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        return [float(value)] * steps
+    try:
+        vals = [float(v) for v in value]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number or a sequence of {steps} numbers") from None
+    if len(vals) != steps:
+        raise ValueError(f"{name} has {len(vals)} entries for {steps} steps")
+    return vals
+
+
+def build_schedule(*, steps, B, H, W, device, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0,
+                   fire=None, seed=None, sample_base=0, offsets=None, sample_offsets=None,
+                   recompute=False) -> Schedule:
+    """Validate a rollout's arguments and build its schedule.  Pure Python: needs neither the
+    library nor a GPU, and raises ``ValueError`` before anything is launched.
+
+    ``message_gain``: None for a model without the graph term, else a number or ``steps`` numbers.
+    ``offsets``: ``steps`` lists of (dy, dx) pairs (the same count every step), or None to call
+    ``sample_offsets()`` once per step in step order (``GraphAugmentation.sample_offsets``: the
+    draws ``steps`` forward calls would make from Python's ``random``, message-off steps included).
+    ``fire``: None (hash masks from ``seed`` when any rate is below 1; ``seed=None`` draws one
+    integer from torch's default CPU generator) or a [steps,B,1,H,W] tensor on ``device``: float32
+    uniforms or uint8 / bool masks."""
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    if isinstance(min_steps, bool) or not isinstance(min_steps, int) or min_steps < 0:
+        raise ValueError(f"min_steps must be a non-negative int, got {min_steps!r}")
+    device = torch.device(device)
+    s = Schedule()
+    s.steps, s.full_steps, s.recompute = steps, min(min_steps, steps), bool(recompute)
+    s.sample_base = int(sample_base)
+    s.fire_rates = _per_step(fire_rate, steps, "fire_rate")
+    s.gains = None if message_gain is None else _per_step(message_gain, steps, "message_gain")
+    # offsets
+    if offsets is None:
+        offsets = [sample_offsets() for _ in range(steps)] if sample_offsets is not None else None
+    elif s.gains is None:
+        raise ValueError("offsets given for a model without the graph term")
+    if offsets is None:
+        s.offsets, s.k = None, 0
+    else:
+        offsets = [list(o) for o in offsets]
+        if len(offsets) != steps:
+            raise ValueError(f"offsets has {len(offsets)} entries for {steps} steps")
+        ks = {len(o) for o in offsets}
+        if len(ks) > 1:
+            raise ValueError(f"every step must draw the same number of offsets, got {sorted(ks)}")
+        s.k = ks.pop() if ks else 0
+        if s.k > L.MAX_OFFSETS:
+            raise ValueError(f"at most {L.MAX_OFFSETS} offsets per step (got {s.k})")
+        for o in offsets:
+            for pair in o:
+                if len(pair) != 2 or not all(isinstance(v, int) and -127 <= v <= 127 for v in pair):
+                    raise ValueError(f"offset {pair!r} is not a (dy, dx) pair in the int8 range")
+        s.offsets = [[(int(dy), int(dx)) for dy, dx in o] for o in offsets]
+    # active steps per sample
+    if nsteps is not None:
+        if not isinstance(nsteps, torch.Tensor) or nsteps.dtype != torch.int32 or tuple(nsteps.shape) != (B,):
+            raise ValueError(f"nsteps must be an int32 tensor of shape ({B},)")
+        if nsteps.device != device:
+            raise ValueError(f"nsteps is on {nsteps.device}, the state on {device}")
+        nsteps = nsteps.contiguous()
+    s.nsteps = nsteps
+    # fire
+    s.seed = 0
+    if fire is not None:
+        if not isinstance(fire, torch.Tensor) or tuple(fire.shape) != (steps, B, 1, H, W):
+            raise ValueError(f"fire must be a tensor of shape ({steps}, {B}, 1, {H}, {W})")
+        if fire.device != device:
+            raise ValueError(f"fire is on {fire.device}, the state on {device}")
+        if fire.dtype == torch.float32:
+            s.fire_mode = L.FIRE_RAND_F32
+        elif fire.dtype in (torch.uint8, torch.bool):
+            s.fire_mode = L.FIRE_MASK_U8
+        else:
+            raise ValueError(f"fire must be float32 uniforms or uint8 / bool masks, got {fire.dtype}")
+        fire = fire.contiguous()
+        s.fire = fire.view(torch.uint8) if fire.dtype == torch.bool else fire
+    else:
+        s.fire = None
+        if any(r < 1.0 for r in s.fire_rates):
+            s.fire_mode = L.FIRE_HASH
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            elif isinstance(seed, bool) or not isinstance(seed, int):
+                raise ValueError(f"seed must be an int, got {seed!r}")
+            s.seed = seed
+        else:
+            s.fire_mode = L.FIRE_NONE
+    return s
+
+
+class RolloutCall:
+    """A schedule bound to a descriptor: the C struct with its host arrays kept alive."""
+
+    def __init__(self, desc: L.StepDesc, sched: Schedule):
+        T, k = sched.steps, desc.num_offsets
+        self.desc, self.schedule = desc, sched
+        c = L.RolloutSched()
+        c.steps, c.full_steps = T, sched.full_steps
+        c.flags = L.SCHED_RECOMPUTE if sched.recompute else 0
+        self._keep = []
+        if sched.offsets is not None and k > 0 and T > 0:
+            flat = [v for o in sched.offsets for pair in o for v in pair]
+            arr = (ctypes.c_int8 * len(flat))(*flat)
+            self._keep.append(arr)
+            c.offsets = ctypes.cast(arr, ctypes.c_void_p)
+        if T > 0:
+            fr = (ctypes.c_float * T)(*sched.fire_rates)
+            self._keep.append(fr)
+            c.fire_rate = ctypes.cast(fr, ctypes.c_void_p)
+            if sched.gains is not None:
+                mg = (ctypes.c_float * T)(*sched.gains)
+                self._keep.append(mg)
+                c.message_gain = ctypes.cast(mg, ctypes.c_void_p)
+        c.nsteps = _ptr(sched.nsteps)
+        c.fire = _ptr(sched.fire)
+        self.c = c
+
+    def _sizes(self, fn):
+        n = fn(ctypes.byref(self.desc), ctypes.byref(self.c))
+        if n == 0:
+            d = self.desc
+            raise L.GncaError(f"unsupported rollout shape: B={d.B} C={d.C} H={d.H} W={d.W} hidden={d.hidden}")
+        return n
+
+    def forward(self, weights, x, want_tape: bool):
+        """(x_final, tape or None).  ``want_tape=False`` is the no-grad form of the same schedule."""
+        lib = L.load()
+        out = torch.empty_like(x)
+        tape = None
+        if want_tape:
+            # (0 steps record nothing: a 256-byte tape keeps the pointer valid)
+            nb = lib.gnca_rollout_tape_bytes(ctypes.byref(self.desc), ctypes.byref(self.c))
+            tape = torch.empty(max(nb, 256), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(self._sizes(lib.gnca_rollout_fwd_workspace_bytes), dtype=torch.uint8, device=x.device)
+        rc = lib.gnca_rollout_fwd_f32(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c),
+                                      x.data_ptr(), out.data_ptr(), _ptr(tape), 0 if tape is None else tape.numel(),
+                                      ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+        L.check(rc, "gnca_rollout_fwd_f32")
+        return out, tape
+
+    def backward(self, weights, tape, gy, want: dict | None = None, out: dict | None = None):
+        """(gx, {name: grad}) of the rollout that recorded ``tape`` (``want`` / ``out`` as in
+        ``step_backward``)."""
+        lib = L.load()
+        gy = _dev_f32(gy, "grad_output")
+        gx = torch.empty_like(gy)
+        g = L.Grads()
+        given, grads = out or {}, {}
+        for name, p in (want or {}).items():
+            t = given.get(name)
+            if t is None:
+                t = torch.empty(p.shape, dtype=torch.float32, device=gy.device)
+            elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
+            grads[name] = t
+            setattr(g, GRAD_FIELDS[name], t.data_ptr())
+        ws = torch.empty(self._sizes(lib.gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=gy.device)
+        rc = lib.gnca_rollout_bwd_f32(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c),
+                                      tape.data_ptr(), tape.numel(), gy.data_ptr(), gx.data_ptr(), ctypes.byref(g),
+                                      ws.data_ptr(), ws.numel(), stream_ptr(gy.device))
+        L.check(rc, "gnca_rollout_bwd_f32")
+        return gx, grads

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define GNCA_ABI_VERSION 2
+#define GNCA_ABI_VERSION 3
 #define GNCA_MAX_OFFSETS 128   /* >= (2r+1)^2-9 for r <= 5 (112) */
 
 /* gnca_step_desc.flags */
@@ -308,6 +308,59 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
                       const void* fire, const uint8_t* active, const float* gy, float* gx,
                       const gnca_grads* grads, const void* saved, void* ws, size_t ws_bytes,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Whole-rollout forward and BPTT: `steps` CA steps in one call each way, on a per-step schedule.
+ * The forward writes every step's input state (and, unless GNCA_SCHED_RECOMPUTE, the step's
+ * workspace: update field, GroupNorm partials, zero-pad offset weights and row sums) into `tape`,
+ * one slot per step, each step writing straight into the next slot; the backward walks the tape in
+ * reverse, keeps the weight-gradient partial rows in the workspace across steps (every row is owned
+ * by one (workgroup, wave) and steps arrive in stream order: a deterministic sum, no float
+ * atomics) and reduces them once.  Equivalent to `steps` gnca_step_masked_f32 / gnca_step_f32 calls
+ * and the sum of their gnca_step_bwd_f32 gradients.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_SCHED_RECOMPUTE (1u << 0)  /* tape keeps states only; the backward recomputes K0/K1 */
+
+typedef struct gnca_rollout_sched {
+  int32_t steps;              /* T, host                                                        */
+  int32_t full_steps;         /* steps t < full_steps run every sample whatever nsteps says     */
+  uint32_t flags;
+  const int8_t* offsets;      /* host  [T][2*desc->num_offsets], as gnca_rollout_f32            */
+  const float* fire_rate;     /* host  [T], NULL = desc->fire_rate for every step               */
+  const float* message_gain;  /* host  [T], NULL = desc->message_gain                           */
+  const int32_t* nsteps;      /* DEVICE [B]: sample b takes step t iff t < nsteps[b]; NULL = all */
+  const void* fire;           /* DEVICE [T][B,1,H,W] for GNCA_FIRE_RAND_F32 / MASK_U8; NULL for
+                                 GNCA_FIRE_HASH (rng_step = desc->rng_step + t) / GNCA_FIRE_NONE */
+} gnca_rollout_sched;
+
+/* Bytes of `tape` a rollout of this schedule records (0 on an invalid desc or schedule; 0 steps
+ * record nothing).  Host-only: reads the schedule's host arrays, never nsteps / fire. */
+size_t gnca_rollout_tape_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched);
+
+/* Bytes of device workspace gnca_rollout_fwd_f32 / gnca_rollout_bwd_f32 need (0 on an invalid
+ * desc or schedule).  Host-only.  The forward's covers the no-tape form (two state buffers). */
+size_t gnca_rollout_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched);
+size_t gnca_rollout_bwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched);
+
+/*
+ * The rollout: x is read, x_final receives the state after the last step (x_final must not alias
+ * x).  tape: >= gnca_rollout_tape_bytes bytes, 256-B aligned, or NULL for the no-grad form of the
+ * same schedule (the states then alternate between two buffers in `ws`).  nsteps is turned into
+ * the per-step active masks on the device (one launch); it is never read on the host.
+ */
+int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
+                         const gnca_rollout_sched* sched, const float* x, float* x_final, void* tape,
+                         size_t tape_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * BPTT through the rollout that wrote `tape` (same desc, weights and schedule, the tape unmodified
+ * since): gy = dL/d x_final, gx = dL/dx (must not alias gy), grads written once (overwritten, in
+ * the layouts of gnca_grads; a NULL pointer skips that gradient; grads itself may be NULL).
+ */
+int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
+                         const gnca_rollout_sched* sched, const void* tape, size_t tape_bytes,
+                         const float* gy, float* gx, const gnca_grads* grads, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Step-adjacent batch op: damage (src/utils/damage.py:15-138).  ONE damage kind for the whole
