@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNCA_LIB_PATH: an alternative build of the same library (A/B measurement runs only)
 LIB_PATH = os.environ.get("GNCA_LIB_PATH") or os.path.join(_HERE, "libgnca.so")
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 MAX_OFFSETS = 128
 
 GRAPH = 1 << 0
@@ -69,6 +69,15 @@ class RolloutSched(ctypes.Structure):
 SCHED_RECOMPUTE = 1 << 0
 
 
+class TraceArgs(ctypes.Structure):
+    """Mirror of gnca_trace_args (include/gnca.h): offsets / record are HOST arrays read during the
+    call, frames / attn are device pointers."""
+    _fields_ = [("steps", ctypes.c_int32), ("num_records", ctypes.c_int32),
+                ("frame_channels", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("offsets", ctypes.c_void_p), ("record", ctypes.c_void_p),
+                ("frames", ctypes.c_void_p), ("attn", ctypes.c_void_p)]
+
+
 class DamageDesc(ctypes.Structure):
     """Mirror of gnca_damage_desc (include/gnca.h)."""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -86,7 +95,8 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_loss_premult_bwd_f32", "gnca_k1_variant", "gnca_rollout_stamped_f32",
            "gnca_rollout_ex_f32", "gnca_bb_variant", "gnca_rollout_tape_bytes",
            "gnca_rollout_fwd_workspace_bytes", "gnca_rollout_bwd_workspace_bytes",
-           "gnca_rollout_fwd_f32", "gnca_rollout_bwd_f32")
+           "gnca_rollout_fwd_f32", "gnca_rollout_bwd_f32", "gnca_attention_workspace_bytes",
+           "gnca_attention_f32", "gnca_rollout_trace_workspace_bytes", "gnca_rollout_trace_f32")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -174,6 +184,16 @@ def load(path: str = LIB_PATH):
                                          ctypes.POINTER(RolloutSched), vp, sz, vp, vp,
                                          ctypes.POINTER(Grads), vp, sz, vp]
     v = lib.gnca_abi_version()
+    if v == ABI_VERSION:   # (an older library lacks these symbols: report the version instead)
+        lib.gnca_attention_workspace_bytes.restype = sz
+        lib.gnca_attention_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc)]
+        lib.gnca_attention_f32.restype = ctypes.c_int
+        lib.gnca_attention_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights), vp, vp, vp, sz, vp]
+        lib.gnca_rollout_trace_workspace_bytes.restype = sz
+        lib.gnca_rollout_trace_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(TraceArgs)]
+        lib.gnca_rollout_trace_f32.restype = ctypes.c_int
+        lib.gnca_rollout_trace_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                               ctypes.POINTER(TraceArgs), vp, vp, vp, sz, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

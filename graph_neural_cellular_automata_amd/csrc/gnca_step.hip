@@ -2830,4 +2830,387 @@ int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------
+// The attention map as a side computation on a state.  In graph_augmentation.py:160-166
+// the map is the channel mean of |w_o * src(q-o) * M(q-o)| summed over the offsets; with w_o >= 0 and
+// src in {0, 1} that is
+//   raw(q) = sum_o w_o * S(q - o),   S(p) = A_send(p) * (1/C) * sum_c |(W_M x(p) + b_M)_c|,
+// so one scalar plane S per sample and k taps of it per cell, instead of one W_M product per offset per
+// cell.  Three light launches (plus K0 for the zero-padded shift's per-sample offset weights):
+//   gnca_attn_sfield  S [B,H,W]          one thread per cell, W_M / b_M broadcast from LDS
+//   gnca_attn_gather  raw -> attn, and (min, max) per workgroup
+//   gnca_attn_finish  per-sample reduction of the partials and the in-place normalisation
+// The S plane of a sample is a few KB to a few hundred KB and is read k times per cell right after it
+// was written: the taps go to it directly (L2-resident), which holds for every int8 offset radius and
+// for a halo larger than the canvas; an LDS tile + halo would not fit the larger radii.  No atomics:
+// min / max are order-independent and every partial has one owner.
+// ---------------------------------------------------------------------------------------------
+namespace gnca {
+
+struct AttnArgs {
+  const float* x;
+  const float* wm;
+  const float* bm;
+  const float* offw;   // [B * k] per-sample offset weights (zero-padded shift), or nullptr: uniform_w
+  float* S;            // [B, H, W]
+  float* attn;         // [B, H, W]
+  float* mm;           // [B, nblk, 2]
+  int B, C, H, W, k, nblk;
+  int zp, a2a;
+  float gthr, uniform_w;
+  // torus: (dy mod H, dx mod W) in [0, H) x [0, W); zero-padded shift: (dy, 0) as given
+  int16_t oy[GNCA_MAX_OFFSETS], ox[GNCA_MAX_OFFSETS];
+};
+
+struct AttnLayout {
+  size_t off_offw, off_rs, off_S, off_mm, bytes;
+  int k, nblk;
+  bool on, zp;
+};
+
+static bool attn_layout(const gnca_step_desc* d, AttnLayout* L) {
+  if (!d || d->B <= 0 || d->C < 4 || d->C > 32 || d->H <= 0 || d->W <= 0) return false;
+  if (d->num_offsets < 0 || d->num_offsets > GNCA_MAX_OFFSETS) return false;
+  if ((long)d->H * d->W > (1L << 28)) return false;   // int cell indices
+  const bool graph = (d->flags & GNCA_GRAPH) != 0;
+  L->k = graph ? d->num_offsets : 0;
+  L->on = L->k > 0;
+  L->zp = L->on && (d->flags & GNCA_ZERO_PAD_SHIFT) != 0;
+  if (L->zp) {   // K0's limits (make_plan)
+    if (d->d_model <= 0) return false;
+    if (((size_t)d->C * d->H + d->C + d->d_model + L->k) * sizeof(double) > 64 * 1024) return false;
+  }
+  const size_t HW = (size_t)d->H * d->W;
+  L->nblk = (int)((HW + kThreads - 1) / kThreads);
+  size_t o = 0;
+  auto carve = [&o](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  L->off_offw = carve((size_t)d->B * (L->k > 0 ? L->k : 1) * sizeof(float));
+  L->off_rs = carve(L->zp ? (size_t)d->B * d->C * d->H * sizeof(double) : 0);
+  L->off_S = carve(L->on ? (size_t)d->B * HW * sizeof(float) : 0);
+  L->off_mm = carve(L->on ? (size_t)d->B * L->nblk * 2 * sizeof(float) : 0);
+  L->bytes = o;
+  return true;
+}
+
+// S(p) for every cell: CP = the channel count rounded up to 16 (registers hold the cell's channels)
+template <int CP>
+__global__ __launch_bounds__(kThreads) void gnca_attn_sfield(const AttnArgs a) {
+  __shared__ float wms[CP * CP];
+  __shared__ float bms[CP];
+  const int C = a.C, H = a.H, W = a.W, HW = H * W;
+  for (int e = threadIdx.x; e < CP * CP; e += kThreads) {
+    const int co = e / CP, ci = e - co * CP;
+    wms[e] = (co < C && ci < C) ? a.wm[co * C + ci] : 0.f;
+  }
+  for (int e = threadIdx.x; e < CP; e += kThreads) bms[e] = e < C ? a.bm[e] : 0.f;
+  __syncthreads();
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= HW) return;
+  const int i = p / W, j = p - i * W;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    const float* xb = a.x + (size_t)b * C * HW;
+    bool send = true;
+    if (a.a2a) {
+      // 3x3 max-pool of alpha with -inf padding: the window clamped at the image edge repeats an
+      // in-window value (the same max)
+      const float* al = xb + (size_t)3 * HW;
+      const int r0 = (i > 0 ? i - 1 : i) * W, r1 = i * W, r2 = (i < H - 1 ? i + 1 : i) * W;
+      const int c0 = j > 0 ? j - 1 : j, c2 = j < W - 1 ? j + 1 : j;
+      float mx = fmaxf(fmaxf(al[r0 + c0], al[r0 + j]), al[r0 + c2]);
+      mx = fmaxf(mx, fmaxf(fmaxf(al[r1 + c0], al[r1 + j]), al[r1 + c2]));
+      mx = fmaxf(mx, fmaxf(fmaxf(al[r2 + c0], al[r2 + j]), al[r2 + c2]));
+      send = mx > a.gthr;
+    }
+    float s = 0.f;
+    if (send) {   // (a dead sender's S is 0 whatever its message)
+      float xv[CP];
+#pragma unroll
+      for (int c = 0; c < CP; ++c) xv[c] = c < C ? xb[(size_t)c * HW + p] : 0.f;
+      for (int co = 0; co < C; ++co) {
+        float m = bms[co];
+#pragma unroll
+        for (int c = 0; c < CP; ++c) m = fmaf(wms[co * CP + c], xv[c], m);
+        s += fabsf(m);
+      }
+      s /= (float)C;
+    }
+    a.S[(size_t)b * HW + p] = s;
+  }
+}
+
+// workgroup (min, max) over the cells of one block (values of threads with ok == false are ignored)
+__device__ inline void attn_block_minmax(float mn, float mx, float* red, float* out2) {
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, s));
+    mx = fmaxf(mx, __shfl_xor(mx, s));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();   // (the previous use of red[])
+  if (lane == 0) { red[2 * wave] = mn; red[2 * wave + 1] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w_ = 1; w_ < kThreads / 64; ++w_) {
+      mn = fminf(mn, red[2 * w_]);
+      mx = fmaxf(mx, red[2 * w_ + 1]);
+    }
+    out2[0] = mn;
+    out2[1] = mx;
+  }
+}
+
+// raw(q) = sum_o w_o S(q - o), o = 0 .. k-1 in order; torus-wrapped, or (zero-padded shift) rows only
+// and zero outside the image
+__global__ __launch_bounds__(kThreads) void gnca_attn_gather(const AttnArgs a) {
+  __shared__ float red[2 * (kThreads / 64)];
+  const int H = a.H, W = a.W, HW = H * W, k = a.k;
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  const bool ok = p < HW;
+  const int pc = ok ? p : HW - 1;
+  const int i = pc / W, j = pc - i * W;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    const float* Sb = a.S + (size_t)b * HW;
+    float raw = 0.f;
+    if (a.zp) {
+      const float* wb = a.offw + (size_t)b * k;
+      for (int o = 0; o < k; ++o) {
+        const int ii = i - a.oy[o];
+        const float s = (ii >= 0 && ii < H) ? Sb[ii * W + j] : 0.f;
+        raw += wb[o] * s;
+      }
+    } else {
+      for (int o = 0; o < k; ++o) {
+        int ii = i - a.oy[o], jj = j - a.ox[o];
+        ii = ii < 0 ? ii + H : ii;
+        jj = jj < 0 ? jj + W : jj;
+        raw += a.uniform_w * Sb[ii * W + jj];
+      }
+    }
+    if (ok) a.attn[(size_t)b * HW + p] = raw;
+    attn_block_minmax(ok ? raw : INFINITY, ok ? raw : -INFINITY, red,
+                      a.mm + ((size_t)b * a.nblk + blockIdx.x) * 2);
+  }
+}
+
+// attn = (raw - min_b) / (max_b - min_b + 1e-8): every workgroup reduces its sample's partials itself
+__global__ __launch_bounds__(kThreads) void gnca_attn_finish(float* attn, const float* mm, int B, int nblk, int HW) {
+  __shared__ float red[2 * (kThreads / 64)];
+  __shared__ float res[2];
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (int t = threadIdx.x; t < nblk; t += kThreads) {
+      mn = fminf(mn, mm[((size_t)b * nblk + t) * 2]);
+      mx = fmaxf(mx, mm[((size_t)b * nblk + t) * 2 + 1]);
+    }
+    attn_block_minmax(mn, mx, red, res);
+    __syncthreads();
+    const float lo = res[0], den = res[1] - res[0] + 1e-8f;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; p < HW; p += gridDim.x * kThreads) {
+      float* q = attn + (size_t)b * HW + p;
+      *q = (*q - lo) / den;
+    }
+    __syncthreads();   // res[] is rewritten for the next sample
+  }
+}
+
+static int attention_impl(const gnca_step_desc* d, const gnca_weights* w, const float* x, float* attn, void* ws,
+                          size_t ws_bytes, hipStream_t st) {
+  AttnLayout L;
+  if (!attn_layout(d, &L)) return (d && d->C > 32) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (!x || !attn) return GNCA_ERR_INVALID;
+  const size_t HW = (size_t)d->H * d->W;
+  if (!L.on)   // graph off or no offsets: zeros (graph_augmentation.py:141-147)
+    return hipMemsetAsync(attn, 0, (size_t)d->B * HW * sizeof(float), st) == hipSuccess ? GNCA_OK : GNCA_ERR_HIP;
+  if (!w || !w->wm || !w->bm) return GNCA_ERR_INVALID;
+  if (L.zp && (!w->wq || !w->bq || !w->wk || !w->bk || !w->scaling)) return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < L.bytes) return GNCA_ERR_WORKSPACE;
+  char* wsb = reinterpret_cast<char*>(ws);
+  int rc;
+  if (L.zp) {   // the step's own K0: launch_k0 reads only these Plan fields
+    Plan P;
+    memset(&P, 0, sizeof(P));
+    P.k = L.k;
+    P.off_offw = L.off_offw;
+    P.off_rs = L.off_rs;
+    if ((rc = launch_k0(d, w, P, x, wsb, st)) != GNCA_OK) return rc;
+  }
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.wm = w->wm; a.bm = w->bm;
+  a.offw = L.zp ? reinterpret_cast<const float*>(wsb + L.off_offw) : nullptr;
+  a.S = reinterpret_cast<float*>(wsb + L.off_S);
+  a.attn = attn;
+  a.mm = reinterpret_cast<float*>(wsb + L.off_mm);
+  a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W; a.k = L.k; a.nblk = L.nblk;
+  a.zp = L.zp ? 1 : 0;
+  a.a2a = (d->flags & GNCA_ALIVE_TO_ALIVE) ? 1 : 0;
+  a.gthr = d->graph_alpha_thr;
+  a.uniform_w = (float)(1.0 / (double)L.k);
+  for (int o = 0; o < L.k; ++o) {
+    const int dy = d->offsets[2 * o], dx = d->offsets[2 * o + 1];
+    a.oy[o] = (int16_t)(L.zp ? dy : ((dy % d->H) + d->H) % d->H);
+    a.ox[o] = (int16_t)(L.zp ? 0 : ((dx % d->W) + d->W) % d->W);
+  }
+  // torus: the wrapped offsets must fit int16 (canvases up to 32767 rows / columns)
+  if (!L.zp && (d->H > 32767 || d->W > 32767)) return GNCA_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)L.nblk, (unsigned)std::min(d->B, 65535));
+  if (d->C <= 16)
+    hipLaunchKernelGGL(gnca_attn_sfield<16>, grid, dim3(kThreads), 0, st, a);
+  else
+    hipLaunchKernelGGL(gnca_attn_sfield<32>, grid, dim3(kThreads), 0, st, a);
+  if ((rc = check_launch()) != GNCA_OK) return rc;
+  hipLaunchKernelGGL(gnca_attn_gather, grid, dim3(kThreads), 0, st, a);
+  if ((rc = check_launch()) != GNCA_OK) return rc;
+  const dim3 gridn((unsigned)std::min(L.nblk, 64), grid.y);
+  hipLaunchKernelGGL(gnca_attn_finish, gridn, dim3(kThreads), 0, st, attn, a.mm, d->B, L.nblk, (int)HW);
+  return check_launch();
+}
+
+// frames[b, c, :] = state[b, c, :] for c < fc: n = fc * H * W floats per sample out of CHW
+template <int V>
+__global__ __launch_bounds__(kThreads) void gnca_k_frame_copy(const float* src, float* dst, int B, long n, long CHW) {
+  typedef float fv __attribute__((ext_vector_type(V)));
+  const long nv = n / V;
+  for (int b = blockIdx.y; b < B; b += gridDim.y)
+    for (long e = (long)blockIdx.x * kThreads + threadIdx.x; e < nv; e += (long)gridDim.x * kThreads)
+      *reinterpret_cast<fv*>(dst + (size_t)b * n + V * e) = *reinterpret_cast<const fv*>(src + (size_t)b * CHW + V * e);
+}
+
+static int frame_copy(const float* src, float* dst, int B, int fc, int C, size_t HW, hipStream_t st) {
+  const long n = (long)fc * HW, CHW = (long)C * HW;
+  if (fc == C)
+    return hipMemcpyAsync(dst, src, (size_t)B * CHW * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess
+               ? GNCA_OK : GNCA_ERR_HIP;
+  const bool v4 = n % 4 == 0 && CHW % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const long nv = v4 ? n / 4 : n;
+  const dim3 grid((unsigned)std::min<long>((nv + kThreads - 1) / kThreads, 1024), (unsigned)std::min(B, 65535));
+  if (v4)
+    hipLaunchKernelGGL(gnca_k_frame_copy<4>, grid, dim3(kThreads), 0, st, src, dst, B, n, CHW);
+  else
+    hipLaunchKernelGGL(gnca_k_frame_copy<1>, grid, dim3(kThreads), 0, st, src, dst, B, n, CHW);
+  return check_launch();
+}
+
+// [state A | state B | scratch | rollout workspace | attention workspace]
+struct TraceLayout {
+  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, bytes;
+};
+
+static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, TraceLayout* L) {
+  if (!d || !a || a->steps < 0 || a->num_records < 0 || a->flags != 0) return false;
+  if (a->num_records > 0 && !a->record) return false;
+  for (int r = 0; r < a->num_records; ++r) {
+    if (a->record[r] < 1 || a->record[r] > a->steps) return false;
+    if (r > 0 && a->record[r] <= a->record[r - 1]) return false;
+  }
+  gnca_step_desc dt = *d;
+  dt.flags &= ~GNCA_ATTENTION;
+  if (a->frame_channels < 1 || a->frame_channels > d->C) return false;
+  // the step workspace of the widest plan: a runtime-geometry K1 picks its tiles from the step's own
+  // offset radius, so the size can differ from step to step
+  L->ws = gnca_workspace_bytes(&dt);
+  const int k = d->num_offsets;
+  if ((d->flags & GNCA_GRAPH) && k > 0 && k <= GNCA_MAX_OFFSETS && a->offsets)
+    for (int t = 0; t < a->steps && L->ws; ++t) {
+      memcpy(dt.offsets, a->offsets + (size_t)t * 2 * k, 2 * k);
+      const size_t n = gnca_workspace_bytes(&dt);
+      L->ws = n == 0 ? 0 : std::max(L->ws, n);
+    }
+  if (L->ws == 0) return false;
+  L->ws = (L->ws + 255) & ~(size_t)255;
+  L->attn_ws = 0;
+  if (a->attn) {
+    AttnLayout A;
+    if (!attn_layout(&dt, &A)) return false;
+    L->attn_ws = A.bytes;
+  }
+  L->state = ((size_t)d->B * d->C * d->H * d->W * sizeof(float) + 255) & ~(size_t)255;
+  L->off_scratch = 2 * L->state;
+  L->off_ws = 3 * L->state;
+  L->off_attn = L->off_ws + L->ws;
+  L->bytes = L->off_attn + L->attn_ws;
+  return true;
+}
+
+}  // namespace gnca
+
+extern "C" {
+
+size_t gnca_attention_workspace_bytes(const gnca_step_desc* desc) {
+  AttnLayout L;
+  return attn_layout(desc, &L) ? std::max<size_t>(L.bytes, 256) : 0;
+}
+
+int gnca_attention_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x, float* attn, void* ws,
+                       size_t ws_bytes, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  return attention_impl(desc, w, x, attn, ws, ws_bytes, st);
+}
+
+size_t gnca_rollout_trace_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args) {
+  TraceLayout L;
+  return trace_layout(desc, args, &L) ? L.bytes : 0;
+}
+
+int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                           const float* x, float* x_final, void* ws, size_t ws_bytes, void* stream) {
+  if (!desc || !w || !args || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
+  TraceLayout L;
+  if (!trace_layout(desc, args, &L)) return GNCA_ERR_INVALID;
+  const int T = args->steps, R = args->num_records, fc = args->frame_channels;
+  if (R > 0 && !args->frames) return GNCA_ERR_INVALID;
+  if (desc->fire_mode != GNCA_FIRE_NONE && desc->fire_mode != GNCA_FIRE_HASH) return GNCA_ERR_INVALID;
+  const int k = desc->num_offsets;
+  const bool offs = (desc->flags & GNCA_GRAPH) && k > 0;
+  if (offs && T > 0 && !args->offsets) return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < L.bytes) return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  char* wsb = reinterpret_cast<char*>(ws);
+  float* buf[2] = {reinterpret_cast<float*>(wsb), reinterpret_cast<float*>(wsb + L.state)};
+  float* scratch = reinterpret_cast<float*>(wsb + L.off_scratch);
+  const size_t HW = (size_t)desc->H * desc->W;
+  gnca_step_desc dt = *desc;
+  dt.flags &= ~GNCA_ATTENTION;
+  const bool maps = args->attn != nullptr;
+  if (T == 0)
+    return hipMemcpyAsync(x_final, x, (size_t)desc->B * desc->C * HW * sizeof(float), hipMemcpyDeviceToDevice,
+                          st) == hipSuccess ? GNCA_OK : GNCA_ERR_HIP;
+  // Pieces of the plain rollout: [t0, t1) ends at every record point (the frame is the state after step
+  // record[r]) and, with maps, also one step before it (the map of step record[r] is computed from
+  // that step's input state).  Every piece is a whole rollout_impl call on the caller's stream (its
+  // sub-batch streams fork and join inside it), so frames and maps follow in stream order.
+  const float* cur = x;
+  int t0 = 0, r = 0, nb = 0;
+  while (t0 < T) {
+    int rc;
+    if (maps && r < R && args->record[r] == t0 + 1) {   // the map of step t0 + 1, from its input state
+      if (offs) memcpy(dt.offsets, args->offsets + (size_t)t0 * 2 * k, 2 * k);
+      if ((rc = attention_impl(&dt, w, cur, args->attn + (size_t)r * desc->B * HW, wsb + L.off_attn, L.attn_ws,
+                               st)) != GNCA_OK)
+        return rc;
+    }
+    int t1 = T;
+    if (r < R) t1 = (maps && args->record[r] - 1 > t0) ? args->record[r] - 1 : args->record[r];
+    float* dst = t1 == T ? x_final : buf[nb];
+    dt.rng_step = desc->rng_step + t0;
+    rc = rollout_impl(&dt, w, t1 - t0, offs ? args->offsets + (size_t)t0 * 2 * k : nullptr, cur, dst, scratch,
+                      wsb + L.off_ws, L.ws, stream, nullptr, 0, 0u);
+    if (rc != GNCA_OK) return rc;
+    if (r < R && args->record[r] == t1) {
+      if ((rc = frame_copy(dst, args->frames + (size_t)r * desc->B * fc * HW, desc->B, fc, desc->C, HW, st)) !=
+          GNCA_OK)
+        return rc;
+      ++r;
+    }
+    cur = dst;
+    nb ^= 1;
+    t0 = t1;
+  }
+  return GNCA_OK;
+}
+
+}  // extern "C"
+
 #endif  // GNCA_K1_PROBE

@@ -286,27 +286,11 @@ class _RolloutFn(torch.autograd.Function):
         return (gx if ctx.needs_input_grad[0] else None, None, None, None, None, None, flats[0], flats[1], None)
 
 
-def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
-                message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0, offsets=None,
-                recompute=False):
-    """``steps`` CA steps in one native call (and, with grad, one autograd node): the shared body of
-    ``NeuralCA.rollout`` / ``NeuralCAGraph.rollout``."""
-    x = S.check_state(x, model.n_channels)
+def _rollout_desc(model: nn.Module, x, steps: int, graph, hidden_only: bool, sched):
+    """(desc, weights, keep, tensors) of a rollout of ``sched`` on ``x``: the shared front of
+    ``run_rollout`` and ``run_trace``."""
     B, C, H, W = x.shape
-    flags = 0
-    norm = model._modules["norm"]
-    eps = 1e-3
-    if isinstance(norm, nn.GroupNorm):
-        if norm.num_groups != 1 or not norm.affine:
-            raise ValueError("only GroupNorm(1, C, affine=True) is supported (ncagraph.py:68)")
-        flags |= L.USE_GROUPNORM
-        eps = norm.eps
-    elif not isinstance(norm, nn.Identity):
-        raise ValueError(f"unsupported norm module {type(norm).__name__}")
-    sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                             sample_base=sample_base, offsets=offsets,
-                             sample_offsets=None if graph is None else graph.sample_offsets, recompute=recompute)
+    flags, eps = _check_norm(model)
     tensors = _step_tensors(model, graph)
     d_model = 1
     graph_thr = None
@@ -330,6 +314,34 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
     desc.rng_seed = sched.seed & 0xFFFFFFFFFFFFFFFF
     desc.sample_base = sched.sample_base
     w, keep = S.make_weights(tensors)
+    return desc, w, keep, tensors
+
+
+def _check_norm(model: nn.Module):
+    """(flags, eps) of the model's norm module, or ValueError for one the step does not support."""
+    norm = model._modules["norm"]
+    if isinstance(norm, nn.GroupNorm):
+        if norm.num_groups != 1 or not norm.affine:
+            raise ValueError("only GroupNorm(1, C, affine=True) is supported (ncagraph.py:68)")
+        return L.USE_GROUPNORM, norm.eps
+    if not isinstance(norm, nn.Identity):
+        raise ValueError(f"unsupported norm module {type(norm).__name__}")
+    return 0, 1e-3
+
+
+def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
+                message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0, offsets=None,
+                recompute=False):
+    """``steps`` CA steps in one native call (and, with grad, one autograd node): the shared body of
+    ``NeuralCA.rollout`` / ``NeuralCAGraph.rollout``."""
+    x = S.check_state(x, model.n_channels)
+    B, C, H, W = x.shape
+    _check_norm(model)   # (before the schedule draws its offsets)
+    sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                             sample_base=sample_base, offsets=offsets,
+                             sample_offsets=None if graph is None else graph.sample_offsets, recompute=recompute)
+    desc, w, keep, tensors = _rollout_desc(model, x, steps, graph, hidden_only, sched)
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors.values())):
         core, gpack = param_packs(model, tensors)
         tc = core.token if core is not None else None
@@ -340,3 +352,43 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
         return S.rollout(desc, w, x, steps, sched.offsets or [])
     out, _ = S.RolloutCall(desc, sched).forward(w, x, want_tape=False)
     return out
+
+
+class TraceResult:
+    """What ``trace()`` returns: ``x_final`` [B,C,H,W], ``frames`` [R,B,channels,H,W] (the state after
+    each recorded step), ``steps`` (the R recorded step indices, counted from 1 within this call) and
+    ``attention`` [R,B,H,W] (the map of each recorded step) or None.  All detached."""
+
+    __slots__ = ("x_final", "frames", "steps", "attention")
+
+    def __init__(self, x_final, frames, steps, attention):
+        self.x_final, self.frames, self.steps, self.attention = x_final, frames, steps, attention
+
+    def __repr__(self):
+        return (f"TraceResult(steps={self.steps}, frames={tuple(self.frames.shape)}, "
+                f"attention={None if self.attention is None else tuple(self.attention.shape)})")
+
+
+def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, every=1, record=None,
+              channels=4, return_attention=False, fire_rate=1.0, message_gain=None, seed=None, sample_base=0,
+              first_step=0, offsets=None) -> TraceResult:
+    """The shared body of ``NeuralCA.trace`` / ``NeuralCAGraph.trace``: a no-grad rollout that records
+    frames (and attention maps) in one native call."""
+    if x.dim() != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    _check_norm(model)
+    # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
+    plan = S.build_trace(steps=steps, B=B, C=C, H=H, W=W, device=x.device, every=every, record=record,
+                         channels=channels, return_attention=return_attention, fire_rate=fire_rate,
+                         message_gain=message_gain, seed=seed, sample_base=sample_base, first_step=first_step,
+                         offsets=offsets, sample_offsets=None if graph is None else graph.sample_offsets)
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)
+        sched = plan.schedule
+        desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+        desc.rng_step = plan.first_step
+        out, frames, attn = S.trace(desc, w, x, steps, sched.offsets or [], plan.record, plan.channels,
+                                    want_attention=plan.attention)
+        del keep
+    return TraceResult(out, frames, list(plan.record), attn)

@@ -97,3 +97,20 @@ class GraphAugmentation(nn.Module):
         m, attn = S.message(desc, w, x, want_attention=return_attention_map)
         del keep
         return (m, attn) if return_attention_map else m
+
+    @torch.no_grad()
+    def attention_map(self, x: torch.Tensor, offsets=None) -> torch.Tensor:
+        """The normalised attention map [B,H,W] that ``forward(x, return_attention_map=True)`` returns
+        for these offsets, alone (extension, not in the reference): a light side computation on the
+        state, no message.  ``offsets=None`` draws ``sample_offsets()`` (one ``random.sample``), else a
+        list of (dy, dx) pairs.  No gradient."""
+        x = S.check_state(x.detach(), self.n_channels)
+        chosen = self.sample_offsets() if offsets is None else [(int(dy), int(dx)) for dy, dx in offsets]
+        B, C, H, W = x.shape
+        desc = S.make_desc(B=B, C=C, H=H, W=W, hidden=1, d_model=self.d_model, offsets=chosen,
+                           flags=self.flags(False), update_gain=0.0, alpha_thr=self.alpha_thr,
+                           message_gain=1.0, fire_rate=1.0, fire_mode=L.FIRE_NONE)
+        w, keep = S.make_weights(self.weight_tensors())
+        attn = S.attention_map(desc, w, x)
+        del keep
+        return attn

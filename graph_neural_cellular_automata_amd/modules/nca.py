@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import run_rollout, run_step
+from ._stepper import TraceResult, run_rollout, run_step, run_trace
 from .perception import FixedSobelPerception
 
 
@@ -42,3 +42,18 @@ class NeuralCA(nn.Module):
         ``NeuralCAGraph.rollout`` (no ``message_gain`` / ``offsets`` here)."""
         return run_rollout(self, x, steps, None, False, fire_rate=fire_rate, nsteps=nsteps, min_steps=min_steps,
                            fire=fire, seed=seed, sample_base=sample_base, recompute=recompute)
+
+    def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
+              return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
+              sample_base: int = 0, first_step: int = 0, offsets=None) -> TraceResult:
+        """``steps`` CA steps in one native call that also records frames: see ``NeuralCAGraph.trace``
+        (same arguments and result; always under ``no_grad``, detached tensors).  The classic model
+        has no graph term: ``return_attention=True``, a ``message_gain`` or ``offsets`` raise
+        ``ValueError``."""
+        if return_attention:
+            raise ValueError("return_attention: NeuralCA has no graph term, so no attention map")
+        if message_gain is not None:
+            raise ValueError("message_gain given for a model without the graph term")
+        return run_trace(self, x, steps, None, False, every=every, record=record, channels=channels,
+                         fire_rate=fire_rate, seed=seed, sample_base=sample_base, first_step=first_step,
+                         offsets=offsets)

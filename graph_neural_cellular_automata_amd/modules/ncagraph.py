@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import run_rollout, run_step
+from ._stepper import TraceResult, run_rollout, run_step, run_trace
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -89,8 +89,36 @@ class NeuralCAGraph(nn.Module):
         ``recompute=True`` halves the tape (the backward recomputes each step's update field).
         Under ``no_grad`` a uniform schedule (one rate, one gain, no ``nsteps``, hash or no fire)
         runs the large-batch rollout pipeline (``gnca_rollout_ex_f32``).  ``return_attention`` is
-        not supported here."""
+        not supported here: ``trace()`` records frames and attention maps."""
         return run_rollout(self, x, steps, self.graph, self.hidden_only, fire_rate=fire_rate,
                            message_gain=self.message_gain if message_gain is None else message_gain,
                            nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
                            offsets=offsets, recompute=recompute)
+
+    def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
+              return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
+              sample_base: int = 0, first_step: int = 0, offsets=None) -> TraceResult:
+        """``steps`` CA steps in one native call that also records (extension, not in the reference):
+        the per-step Python loop of the regeneration diagnostic and the video generators, on the
+        rollout pipeline.  Always runs under ``no_grad`` and returns detached tensors, whatever the
+        caller's grad mode: for gradients use ``rollout()``.
+
+        Returns a ``TraceResult``: ``x_final``; ``frames`` [R,B,channels,H,W], channels
+        ``0..channels-1`` of the state after each recorded step; ``steps``, the recorded step indices
+        (from 1, within this call); ``attention`` [R,B,H,W] with ``return_attention=True``, the
+        normalised map of each recorded step (computed from that step's input state and offsets, as
+        ``forward(..., return_attention=True)`` does), else None.
+
+        ``every=n`` records steps ``n, 2n, ...`` and also ``steps`` when it is not a multiple;
+        ``record`` lists the indices instead (strictly increasing, in ``1..steps``).  The schedule is
+        the uniform one of the no-grad ``rollout()``: one ``fire_rate`` and one ``message_gain``
+        (``None``: ``self.message_gain``), hash fire masks of ``seed`` when the rate is below 1.
+        ``first_step`` is the hash RNG's step base: ``trace(x, 4, seed=s)`` followed by
+        ``trace(x_final, 3, seed=s, first_step=4)`` (and the matching offsets) continues one fire
+        stream, so "grow, damage, regrow" is two calls.  ``offsets=None`` draws
+        ``self.graph.sample_offsets()`` once per step in step order, as ``rollout()`` does.  Bad
+        arguments raise ``ValueError`` before anything is drawn or launched."""
+        return run_trace(self, x, steps, self.graph, self.hidden_only, every=every, record=record,
+                         channels=channels, return_attention=return_attention, fire_rate=fire_rate,
+                         message_gain=self.message_gain if message_gain is None else message_gain, seed=seed,
+                         sample_base=sample_base, first_step=first_step, offsets=offsets)

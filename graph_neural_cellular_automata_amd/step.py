@@ -427,6 +427,118 @@ def build_schedule(*, steps, B, H, W, device, fire_rate=1.0, message_gain=None, 
     return s
 
 
+def expand_record(steps: int, every=1, record=None) -> list:
+    """The recorded step indices of a trace: ``record`` as given (strictly increasing, in
+    ``1..steps``), else ``every, 2*every, ...`` and also ``steps`` when it is not a multiple."""
+    if record is not None:
+        if every != 1:
+            raise ValueError("give either every or record, not both")
+        try:
+            rec = list(record)
+        except TypeError:
+            raise ValueError(f"record must be a sequence of step indices, got {record!r}") from None
+        for r in rec:
+            if isinstance(r, bool) or not isinstance(r, int):
+                raise ValueError(f"record entries must be ints, got {r!r}")
+            if not 1 <= r <= steps:
+                raise ValueError(f"record entry {r} is outside 1..{steps}")
+        if any(b <= a for a, b in zip(rec, rec[1:])):
+            raise ValueError(f"record must be strictly increasing, got {rec}")
+        return rec
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError(f"every must be a positive int, got {every!r}")
+    rec = list(range(every, steps + 1, every))
+    if steps > 0 and steps % every:
+        rec.append(steps)
+    return rec
+
+
+class TracePlan:
+    """A validated trace (``build_trace``): the uniform schedule, the recorded step indices, the
+    frame channel count, the hash-RNG step base and whether maps are wanted."""
+
+    __slots__ = ("schedule", "record", "channels", "first_step", "attention")
+
+
+def build_trace(*, steps, B, C, H, W, device, every=1, record=None, channels=4, return_attention=False,
+                fire_rate=1.0, message_gain=None, seed=None, sample_base=0, first_step=0, offsets=None,
+                sample_offsets=None) -> TracePlan:
+    """Validate a trace's arguments and build its plan.  Pure Python, like ``build_schedule`` (which
+    validates the shared arguments and draws the offsets): raises ``ValueError`` before the library is
+    loaded.  A trace runs the no-grad rollout pipeline, so its schedule must be uniform: one fire
+    rate and one message gain for every step (a per-step list must hold one value), hash or no fire
+    masks."""
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= C:
+        raise ValueError(f"channels must be an int in 1..{C} (the state's channel count), got {channels!r}")
+    if isinstance(first_step, bool) or not isinstance(first_step, int) or first_step < 0:
+        raise ValueError(f"first_step must be a non-negative int, got {first_step!r}")
+    if return_attention and message_gain is None:
+        raise ValueError("return_attention needs the graph term: this model has none")
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    rec = expand_record(steps, every, record)
+    # (before the offsets are drawn: a rejected call leaves Python's random state alone)
+    for name, v in (("fire_rate", fire_rate), ("message_gain", message_gain)):
+        if v is not None and len(set(_per_step(v, steps, name))) > 1:
+            raise ValueError(f"a trace needs a uniform schedule: {name} must be one value for every step")
+    s = build_schedule(steps=steps, B=B, H=H, W=W, device=device, fire_rate=fire_rate, message_gain=message_gain,
+                       seed=seed, sample_base=sample_base, offsets=offsets, sample_offsets=sample_offsets)
+    if not s.uniform:
+        raise ValueError("a trace needs a uniform schedule")
+    p = TracePlan()
+    p.schedule, p.record, p.channels, p.first_step, p.attention = s, rec, channels, first_step, bool(return_attention)
+    return p
+
+
+def attention_map(desc, weights, x):
+    """The normalised attention map [B,H,W] of state ``x`` for ``desc``'s offsets
+    (gnca_attention_f32): a side computation, no step."""
+    lib = L.load()
+    attn = torch.empty(desc.B, desc.H, desc.W, dtype=torch.float32, device=x.device)
+    n = lib.gnca_attention_workspace_bytes(ctypes.byref(desc))
+    if n == 0:
+        raise L.GncaError(f"unsupported attention-map shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"k={desc.num_offsets}")
+    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    rc = lib.gnca_attention_f32(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), attn.data_ptr(),
+                                ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+    L.check(rc, "gnca_attention_f32")
+    return attn
+
+
+def trace(desc, weights, x, steps: int, offsets_per_step: list, record: list, channels: int,
+          want_attention: bool = False):
+    """``steps`` no-grad steps in one C call that also records (gnca_rollout_trace_f32): returns
+    ``(x_final, frames [R,B,channels,H,W], attention [R,B,H,W] or None)``."""
+    lib = L.load()
+    k = desc.num_offsets
+    flat = [v for offs in offsets_per_step for o in offs for v in o]
+    if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
+        raise ValueError("offsets_per_step must hold k pairs for every step")
+    arr = (ctypes.c_int8 * len(flat))(*flat) if flat else None
+    R = len(record)
+    rec = (ctypes.c_int32 * max(1, R))(*record)
+    out = torch.empty_like(x)
+    frames = torch.empty(R, desc.B, channels, desc.H, desc.W, dtype=torch.float32, device=x.device)
+    attn = torch.empty(R, desc.B, desc.H, desc.W, dtype=torch.float32, device=x.device) if want_attention else None
+    a = L.TraceArgs()
+    a.steps, a.num_records, a.frame_channels, a.flags = int(steps), R, int(channels), 0
+    a.offsets = ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None
+    a.record = ctypes.cast(rec, ctypes.c_void_p)
+    # (an empty tensor's data_ptr is 0: no record points, nothing is written)
+    a.frames = frames.data_ptr() if R else None
+    a.attn = attn.data_ptr() if (attn is not None and R) else None
+    n = lib.gnca_rollout_trace_workspace_bytes(ctypes.byref(desc), ctypes.byref(a))
+    if n == 0:
+        raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden}")
+    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    rc = lib.gnca_rollout_trace_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), x.data_ptr(),
+                                    out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+    L.check(rc, "gnca_rollout_trace_f32")
+    return out, frames, attn
+
+
 class RolloutCall:
     """A schedule bound to a descriptor: the C struct with its host arrays kept alive."""
 

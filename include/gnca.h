@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define GNCA_ABI_VERSION 3
+#define GNCA_ABI_VERSION 4
 #define GNCA_MAX_OFFSETS 128   /* >= (2r+1)^2-9 for r <= 5 (112) */
 
 /* gnca_step_desc.flags */
@@ -361,6 +361,52 @@ int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
                          const gnca_rollout_sched* sched, const void* tape, size_t tape_bytes,
                          const float* gy, float* gx, const gnca_grads* grads, void* ws,
                          size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The attention map as a side computation, and a rollout that records frames and maps.
+ * -------------------------------------------------------------------------------------------*/
+
+/* Bytes of device workspace gnca_attention_f32 needs for `desc` (0 on an invalid desc). */
+size_t gnca_attention_workspace_bytes(const gnca_step_desc* desc);
+
+/*
+ * The normalised attention map of GraphAugmentation.forward (graph_augmentation.py:160-167) for the
+ * state x and desc's offsets, without the step: attn [B,H,W], min-max normalised per sample.  Reads
+ * desc's B, C (<= 32), H, W, offsets, graph_alpha_thr (d_model for the zero-padded shift) and the
+ * flags GNCA_GRAPH, GNCA_ALIVE_TO_ALIVE, GNCA_ZERO_PAD_SHIFT; every other field is ignored.  Weights:
+ * wm, bm (and wq, bq, wk, bk, scaling for the zero-padded shift's per-sample offset weights).  Graph
+ * off or num_offsets == 0: zeros.  Bitwise reproducible (no atomics).
+ */
+int gnca_attention_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x, float* attn,
+                       void* ws, size_t ws_bytes, void* stream);
+
+typedef struct gnca_trace_args {
+  int32_t steps;              /* T                                                              */
+  int32_t num_records;        /* R                                                              */
+  int32_t frame_channels;     /* channels 0 .. frame_channels-1 of each frame, 1 .. C           */
+  uint32_t flags;             /* reserved: 0                                                    */
+  const int8_t* offsets;      /* host  [T][2*desc->num_offsets], as gnca_rollout_f32            */
+  const int32_t* record;      /* host  [R], strictly increasing, values in 1 .. T               */
+  float* frames;              /* DEVICE [R,B,frame_channels,H,W]: the state after step record[r] */
+  float* attn;                /* DEVICE [R,B,H,W] or NULL: the map of step record[r], computed
+                                 from that step's input state with that step's offsets          */
+} gnca_trace_args;
+
+/* Bytes of device workspace gnca_rollout_trace_f32 needs (0 on an invalid desc or args).  Host-only:
+ * reads args->record, args->offsets (the widest step plan) and whether args->attn is set. */
+size_t gnca_rollout_trace_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args);
+
+/*
+ * gnca_rollout_f32 that also records: the same uniform schedule (one desc, GNCA_FIRE_HASH / NONE,
+ * step t uses args->offsets[t*2*k ..] and rng_step = desc->rng_step + t), issued as pieces of the
+ * plain rollout that end at the record points (and, with maps, one step before them), so every
+ * piece runs the plan gnca_rollout_f32 picks for the shape.  The frames, the maps and x_final are
+ * bitwise those of separate gnca_rollout_f32 / gnca_attention_f32 calls.  Everything is enqueued
+ * from this one call, stream-ordered on `stream`, with no host synchronisation.  x_final must not
+ * alias x.
+ */
+int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                           const float* x, float* x_final, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Step-adjacent batch op: damage (src/utils/damage.py:15-138).  ONE damage kind for the whole
