@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNCA_LIB_PATH: an alternative build of the same library (A/B measurement runs only)
 LIB_PATH = os.environ.get("GNCA_LIB_PATH") or os.path.join(_HERE, "libgnca.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 MAX_OFFSETS = 128
 
 GRAPH = 1 << 0
@@ -78,6 +78,11 @@ class TraceArgs(ctypes.Structure):
                 ("frames", ctypes.c_void_p), ("attn", ctypes.c_void_p)]
 
 
+class TraceMetrics(ctypes.Structure):
+    """Mirror of gnca_trace_metrics (include/gnca.h): device pointers and the target's sample stride."""
+    _fields_ = [("target", ctypes.c_void_p), ("target_bstride", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
 class DamageDesc(ctypes.Structure):
     """Mirror of gnca_damage_desc (include/gnca.h)."""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -96,7 +101,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_ex_f32", "gnca_bb_variant", "gnca_rollout_tape_bytes",
            "gnca_rollout_fwd_workspace_bytes", "gnca_rollout_bwd_workspace_bytes",
            "gnca_rollout_fwd_f32", "gnca_rollout_bwd_f32", "gnca_attention_workspace_bytes",
-           "gnca_attention_f32", "gnca_rollout_trace_workspace_bytes", "gnca_rollout_trace_f32")
+           "gnca_attention_f32", "gnca_rollout_trace_workspace_bytes", "gnca_rollout_trace_f32",
+           "gnca_image_metrics_workspace_bytes", "gnca_image_metrics_f32",
+           "gnca_rollout_trace_metrics_workspace_bytes", "gnca_rollout_trace_metrics_f32")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -194,6 +201,17 @@ def load(path: str = LIB_PATH):
         lib.gnca_rollout_trace_f32.restype = ctypes.c_int
         lib.gnca_rollout_trace_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                ctypes.POINTER(TraceArgs), vp, vp, vp, sz, vp]
+        lib.gnca_image_metrics_workspace_bytes.restype = sz
+        lib.gnca_image_metrics_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.gnca_image_metrics_f32.restype = ctypes.c_int
+        lib.gnca_image_metrics_f32.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, sz, vp]
+        lib.gnca_rollout_trace_metrics_workspace_bytes.restype = sz
+        lib.gnca_rollout_trace_metrics_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(TraceArgs),
+                                                                   ctypes.POINTER(TraceMetrics)]
+        lib.gnca_rollout_trace_metrics_f32.restype = ctypes.c_int
+        lib.gnca_rollout_trace_metrics_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                       ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics),
+                                                       vp, vp, vp, sz, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

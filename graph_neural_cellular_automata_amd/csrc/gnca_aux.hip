@@ -1,5 +1,6 @@
 // gnca_aux.hip — step-adjacent batch ops of the rollout/training loop:
-// the damage curriculum (reference: src/utils/damage.py:15-138), one launch for the whole batch.
+// the damage curriculum (reference: src/utils/damage.py:15-138), one launch for the whole batch,
+// the premultiplied-RGBA loss and the image metrics (mse, pixel-perfect, psnr, ssim).
 //
 // The reference loops over samples on the host, drawing each sample's position with a separate
 // torch.randint(...).item()-style call (a device sync per sample on GPU) and applying a masked
@@ -129,6 +130,190 @@ __global__ __launch_bounds__(kThreads) void gnca_loss_bwd(int B, int H, int W, c
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Image metrics (train_graph_augmented_nca.py:405-422 and skimage's defaults): per image
+// mse / pixel-perfect fraction / psnr / ssim of P = (pred_rgb * pred_alpha, pred_alpha) against the
+// premultiplied target, for the whole batch in one launch.
+//
+// One workgroup per (image, band of kMetBand window rows).  The band's rows of X = clip(P_rgb) and
+// Y = clip(T_rgb) are staged in LDS as fp32, in column chunks of kMetCols windows (+6 halo), so any
+// H and W work.  While staging, each cell a band owns adds its squared errors and its pixel-perfect
+// bit.  Then one thread per (colour channel, window column) walks down the band with running fp64
+// window sums: the 7-tap horizontal sums of the entering row are added and those of the leaving row,
+// kept in a register ring, subtracted (7 taps per moment and window instead of 49).  The tile
+// geometry depends on (H, W) alone and every sum has a fixed order (per thread, xor-shuffle, waves,
+// bands), so an image's result is bitwise the same whatever the batch around it.  The kernel is bound
+// by fp64 VALU issue, not by traffic.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMetWin = 7;                        // skimage's default win_size
+constexpr int kMetBand = 22;                      // window rows per workgroup (72^2: 3 bands)
+constexpr int kMetCols = 72;                      // window columns per chunk (52 KB LDS: 3 WGs per CU)
+constexpr int kMetRin = kMetBand + kMetWin - 1;   // staged rows
+constexpr int kMetCin = kMetCols + kMetWin - 1;   // staged columns
+static_assert(3 * kMetCols <= kThreads, "one thread per (colour channel, window column)");
+
+// the 7-tap sums of x, y, xx, yy, xy along one staged row, in fp64
+__device__ __forceinline__ void met_hsum(const float* xr, const float* yr, double h[5]) {
+  h[0] = h[1] = h[2] = h[3] = h[4] = 0.0;
+#pragma unroll
+  for (int k = 0; k < kMetWin; ++k) {
+    const double x = (double)xr[k], y = (double)yr[k];
+    h[0] += x; h[1] += y; h[2] += x * x; h[3] += y * y; h[4] += x * y;
+  }
+}
+
+// skimage's S for one window (uniform filter, sample covariance, data_range 1) from its five raw
+// sums a = Sx, b = Sy, Sxx, Syy, Sxy, with the 1/49 of the means and the 49/48 of the covariances
+// moved into the constants: mx = a/49 and vx = (49 Sxx - a^2) / (48 * 49), so
+//   S = (2ab + K1)(2 cxy + K2) / ((a^2 + b^2 + K1)(cxx + cyy + K2)),  cxy = 49 Sxy - ab, ...
+// with K1 = 49^2 C1, K2 = 48 * 49 C2 (29 fp64 instructions instead of 40).
+__device__ __forceinline__ double met_ssim_window(const double v[5]) {
+#pragma clang fp contract(off)   // pred == target: numerator and denominator round alike, S == 1
+  constexpr double n = (double)(kMetWin * kMetWin);
+  constexpr double K1 = 1e-4 * n * n, K2 = 9e-4 * n * (n - 1.0);
+  const double ab = v[0] * v[1], aa = v[0] * v[0], bb = v[1] * v[1];
+  const double cxx = fma(n, v[2], -aa), cyy = fma(n, v[3], -bb), cxy = fma(n, v[4], -ab);
+  const double num = fma(2.0, ab, K1) * fma(2.0, cxy, K2);
+  const double den = ((aa + bb) + K1) * ((cxx + cyy) + K2);
+  return num / den;
+}
+
+// sums {squared error over 4 channels, pixel-perfect cells, clipped squared error over rgb, S over
+// windows and colour channels} -> out[0..3]
+__device__ __forceinline__ void met_finish(const double s[4], int H, int W, float* out) {
+  const double HW = (double)H * (double)W;
+  out[0] = (float)(s[0] / (4.0 * HW));
+  out[1] = (float)(s[1] / HW);
+  out[2] = s[2] == 0.0 ? INFINITY : (float)(10.0 * log10(1.0 / (s[2] / (3.0 * HW))));
+  out[3] = (H < kMetWin || W < kMetWin)
+               ? NAN
+               : (float)(s[3] / (3.0 * (double)(H - kMetWin + 1) * (double)(W - kMetWin + 1)));
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_image_metrics(int nb, int H, int W, const float* pred, long pbs,
+                                                               const float* tgt, long tbs, double* part,
+                                                               float* out) {
+  __shared__ float xs[3][kMetRin][kMetCin];
+  __shared__ float ys[3][kMetRin][kMetCin];
+  __shared__ double red[kThreads / 64][4];
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x / nb, band = blockIdx.x - n * nb;
+  const size_t HW = (size_t)H * W;
+  const float* p = pred + (size_t)n * pbs;
+  const float* t = tgt + (size_t)n * tbs;
+  const int OH = H - (kMetWin - 1), OW = W - (kMetWin - 1);   // window rows / columns (<= 0: none)
+  const int o0 = band * kMetBand;                             // first window row = first staged row
+  const int nout = min(kMetBand, OH - o0);                    // window rows of this band (<= 0: none)
+  const bool last_band = band == nb - 1;
+  const int rin = min(kMetRin, H - o0);                       // staged rows
+  const int own_r = last_band ? rin : kMetBand;               // rows whose cells this band counts
+  const int ch = tid / kMetCols, col = tid - ch * kMetCols;
+  double s_se4 = 0.0, s_pp = 0.0, s_se3 = 0.0, s_ss = 0.0;
+  const int nchunk = (max(OW, 1) + kMetCols - 1) / kMetCols;
+  for (int q = 0; q < nchunk; ++q) {
+    const int c0 = q * kMetCols;
+    const int cin = min(kMetCin, W - c0);                     // staged columns
+    const int own_c = q == nchunk - 1 ? cin : kMetCols;       // columns whose cells this chunk counts
+    const int cout = min(kMetCols, OW - c0);                  // window columns (<= 0: none)
+    for (int e = tid; e < rin * kMetCin; e += kThreads) {
+      const int r = e / kMetCin, c = e - r * kMetCin;
+      if (c >= cin) continue;
+      const size_t cell = (size_t)(o0 + r) * W + (size_t)(c0 + c);
+      const float a = p[3 * HW + cell];
+      const bool own = r < own_r && c < own_c;
+      const float da = __fsub_rn(a, t[3 * HW + cell]);
+      bool ok = fabsf(da) < 0.05f;
+      double se4 = (double)a - (double)t[3 * HW + cell];
+      se4 *= se4;
+      double se3 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float pv = __fmul_rn(p[k * HW + cell], a);      // the premultiply, rounded to fp32
+        const float tv = t[k * HW + cell];
+        ok = ok && fabsf(__fsub_rn(pv, tv)) < 0.05f;
+        const double d = (double)pv - (double)tv;
+        se4 += d * d;
+        const float x = fminf(fmaxf(pv, 0.f), 1.f), y = fminf(fmaxf(tv, 0.f), 1.f);
+        const double dc = (double)x - (double)y;
+        se3 += dc * dc;
+        xs[k][r][c] = x;
+        ys[k][r][c] = y;
+      }
+      if (own) {
+        s_se4 += se4;
+        s_se3 += se3;
+        s_pp += ok ? 1.0 : 0.0;
+      }
+    }
+    __syncthreads();
+    if (nout > 0 && ch < 3 && col < cout) {
+      // ring[r % 7] keeps the horizontal sums of staged row r while it is inside the window: every
+      // row's sums are computed once.  The row loop is unrolled by 7 so that the ring stays in registers.
+      double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, ring[kMetWin][5];
+#pragma unroll
+      for (int r = 0; r < kMetWin - 1; ++r) {
+        met_hsum(&xs[ch][r][col], &ys[ch][r][col], ring[r]);
+#pragma unroll
+        for (int m = 0; m < 5; ++m) v[m] += ring[r][m];
+      }
+      for (int ob = 0; ob < nout; ob += kMetWin) {
+#pragma unroll
+        for (int k = 0; k < kMetWin; ++k) {
+          const int o = ob + k;                       // window rows o .. o + 6; o % 7 == k
+          if (o < nout) {
+            constexpr int kw = kMetWin;
+            const int in = (k + kw - 1) % kw;         // the slot of the entering row o + 6
+            met_hsum(&xs[ch][o + kw - 1][col], &ys[ch][o + kw - 1][col], ring[in]);
+#pragma unroll
+            for (int m = 0; m < 5; ++m) v[m] += ring[in][m];
+            s_ss += met_ssim_window(v);
+#pragma unroll
+            for (int m = 0; m < 5; ++m) v[m] -= ring[k][m];   // the leaving row o
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  double s[4] = {s_se4, s_pp, s_se3, s_ss};
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+    for (int off = 32; off > 0; off >>= 1) s[m] += __shfl_xor(s[m], off);
+  if ((tid & 63) == 0)
+    for (int m = 0; m < 4; ++m) red[tid >> 6][m] = s[m];
+  __syncthreads();
+  if (tid == 0) {
+    for (int m = 0; m < 4; ++m) {
+      double v = 0.0;
+      for (int w = 0; w < kThreads / 64; ++w) v += red[w][m];
+      s[m] = v;
+    }
+    if (nb == 1) {
+      met_finish(s, H, W, out + (size_t)n * 4);
+    } else {
+      for (int m = 0; m < 4; ++m) part[((size_t)n * nb + band) * 4 + m] = s[m];
+    }
+  }
+}
+
+// the bands' partial sums of each image, added in band order
+__global__ __launch_bounds__(kThreads) void gnca_image_metrics_finish(int N, int nb, int H, int W,
+                                                                      const double* part, float* out) {
+  const int n = blockIdx.x * kThreads + threadIdx.x;
+  if (n >= N) return;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < nb; ++b)
+    for (int m = 0; m < 4; ++m) s[m] += part[((size_t)n * nb + b) * 4 + m];
+  met_finish(s, H, W, out + (size_t)n * 4);
+}
+
+// bands per image: a function of H alone (0: too many workgroups for one launch)
+int met_bands(int32_t N, int32_t H) {
+  const int OH = H - (kMetWin - 1);
+  const long nb = ((OH > 1 ? OH : 1) + kMetBand - 1) / kMetBand;
+  return nb * (long)N > 0x7fffffffL ? 0 : (int)nb;
+}
+
 }  // namespace
 }  // namespace gnca
 
@@ -177,5 +362,33 @@ extern "C" int gnca_damage_f32(const gnca_damage_desc* d, float* state, const in
     g_last_hip = (int)e;
     return GNCA_ERR_HIP;
   }
+  return GNCA_OK;
+}
+
+extern "C" size_t gnca_image_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  const int nb = met_bands(N, H);
+  return nb > 1 ? (size_t)N * nb * 4 * sizeof(double) : 0;
+}
+
+extern "C" int gnca_image_metrics_f32(int32_t N, int32_t H, int32_t W, const float* pred, int64_t pbs,
+                                      const float* target, int64_t tbs, float* out, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || !pred || !target || !out || pbs < 0 || tbs < 0) return GNCA_ERR_INVALID;
+  const int nb = met_bands(N, H);
+  if (nb == 0) return GNCA_ERR_INVALID;
+  const size_t need = nb > 1 ? (size_t)N * nb * 4 * sizeof(double) : 0;
+  if (need && (!ws || ws_bytes < need || ((uintptr_t)ws & 7))) return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(ws);
+  hipLaunchKernelGGL(gnca_image_metrics, dim3((unsigned)(N * nb)), dim3(kThreads), 0, st, nb, H, W, pred, (long)pbs,
+                     target, (long)tbs, part, out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && nb > 1) {
+    hipLaunchKernelGGL(gnca_image_metrics_finish, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       st, N, nb, H, W, part, out);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
   return GNCA_OK;
 }

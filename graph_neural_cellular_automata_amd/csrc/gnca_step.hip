@@ -3091,12 +3091,13 @@ static int frame_copy(const float* src, float* dst, int B, int fc, int C, size_t
   return check_launch();
 }
 
-// [state A | state B | scratch | rollout workspace | attention workspace]
+// [state A | state B | scratch | rollout workspace | attention workspace | metrics workspace]
 struct TraceLayout {
-  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, bytes;
+  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, off_met, met_ws, bytes;
 };
 
-static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, TraceLayout* L) {
+static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, const gnca_trace_metrics* m,
+                         TraceLayout* L) {
   if (!d || !a || a->steps < 0 || a->num_records < 0 || a->flags != 0) return false;
   if (a->num_records > 0 && !a->record) return false;
   for (int r = 0; r < a->num_records; ++r) {
@@ -3128,38 +3129,24 @@ static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, Trac
   L->off_scratch = 2 * L->state;
   L->off_ws = 3 * L->state;
   L->off_attn = L->off_ws + L->ws;
-  L->bytes = L->off_attn + L->attn_ws;
+  L->off_met = L->off_attn + L->attn_ws;
+  L->met_ws = m ? (gnca_image_metrics_workspace_bytes(d->B, d->H, d->W) + 255) & ~(size_t)255 : 0;
+  L->bytes = L->off_met + L->met_ws;
   return true;
 }
 
-}  // namespace gnca
-
-extern "C" {
-
-size_t gnca_attention_workspace_bytes(const gnca_step_desc* desc) {
-  AttnLayout L;
-  return attn_layout(desc, &L) ? std::max<size_t>(L.bytes, 256) : 0;
-}
-
-int gnca_attention_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x, float* attn, void* ws,
-                       size_t ws_bytes, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  StreamDeviceGuard dg(st);
-  return attention_impl(desc, w, x, attn, ws, ws_bytes, st);
-}
-
-size_t gnca_rollout_trace_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args) {
-  TraceLayout L;
-  return trace_layout(desc, args, &L) ? L.bytes : 0;
-}
-
-int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
-                           const float* x, float* x_final, void* ws, size_t ws_bytes, void* stream) {
+// gnca_rollout_trace_f32 (m == nullptr) / gnca_rollout_trace_metrics_f32
+static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                      const gnca_trace_metrics* m, const float* x, float* x_final, void* ws, size_t ws_bytes,
+                      void* stream) {
   if (!desc || !w || !args || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
   TraceLayout L;
-  if (!trace_layout(desc, args, &L)) return GNCA_ERR_INVALID;
+  if (!trace_layout(desc, args, m, &L)) return GNCA_ERR_INVALID;
   const int T = args->steps, R = args->num_records, fc = args->frame_channels;
-  if (R > 0 && !args->frames) return GNCA_ERR_INVALID;
+  if (R > 0 && !args->frames && !m) return GNCA_ERR_INVALID;
+  // (target and out both NULL: nothing is measured, a trace that may go without frames)
+  if (m && (m->target_bstride < 0 || (m->target == nullptr) != (m->out == nullptr))) return GNCA_ERR_INVALID;
+  const bool measure = m && m->out;
   if (desc->fire_mode != GNCA_FIRE_NONE && desc->fire_mode != GNCA_FIRE_HASH) return GNCA_ERR_INVALID;
   const int k = desc->num_offsets;
   const bool offs = (desc->flags & GNCA_GRAPH) && k > 0;
@@ -3180,7 +3167,7 @@ int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, co
   // Pieces of the plain rollout: [t0, t1) ends at every record point (the frame is the state after step
   // record[r]) and, with maps, also one step before it (the map of step record[r] is computed from
   // that step's input state).  Every piece is a whole rollout_impl call on the caller's stream (its
-  // sub-batch streams fork and join inside it), so frames and maps follow in stream order.
+  // sub-batch streams fork and join inside it), so frames, maps and metrics follow in stream order.
   const float* cur = x;
   int t0 = 0, r = 0, nb = 0;
   while (t0 < T) {
@@ -3199,8 +3186,14 @@ int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, co
                       wsb + L.off_ws, L.ws, stream, nullptr, 0, 0u);
     if (rc != GNCA_OK) return rc;
     if (r < R && args->record[r] == t1) {
-      if ((rc = frame_copy(dst, args->frames + (size_t)r * desc->B * fc * HW, desc->B, fc, desc->C, HW, st)) !=
-          GNCA_OK)
+      if (args->frames &&
+          (rc = frame_copy(dst, args->frames + (size_t)r * desc->B * fc * HW, desc->B, fc, desc->C, HW, st)) !=
+              GNCA_OK)
+        return rc;
+      // the metrics read channels 0..3 of the piece's output state in place
+      if (measure && (rc = gnca_image_metrics_f32(desc->B, desc->H, desc->W, dst, (int64_t)desc->C * (int64_t)HW,
+                                            m->target, m->target_bstride, m->out + (size_t)r * desc->B * 4,
+                                            wsb + L.off_met, L.met_ws, stream)) != GNCA_OK)
         return rc;
       ++r;
     }
@@ -3209,6 +3202,45 @@ int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, co
     t0 = t1;
   }
   return GNCA_OK;
+}
+
+}  // namespace gnca
+
+extern "C" {
+
+size_t gnca_attention_workspace_bytes(const gnca_step_desc* desc) {
+  AttnLayout L;
+  return attn_layout(desc, &L) ? std::max<size_t>(L.bytes, 256) : 0;
+}
+
+int gnca_attention_f32(const gnca_step_desc* desc, const gnca_weights* w, const float* x, float* attn, void* ws,
+                       size_t ws_bytes, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  return attention_impl(desc, w, x, attn, ws, ws_bytes, st);
+}
+
+size_t gnca_rollout_trace_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args) {
+  TraceLayout L;
+  return trace_layout(desc, args, nullptr, &L) ? L.bytes : 0;
+}
+
+int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                           const float* x, float* x_final, void* ws, size_t ws_bytes, void* stream) {
+  return trace_impl(desc, w, args, nullptr, x, x_final, ws, ws_bytes, stream);
+}
+
+size_t gnca_rollout_trace_metrics_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                                  const gnca_trace_metrics* m) {
+  TraceLayout L;
+  return m && trace_layout(desc, args, m, &L) ? L.bytes : 0;
+}
+
+int gnca_rollout_trace_metrics_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                                   const gnca_trace_metrics* m, const float* x, float* x_final, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (!m) return GNCA_ERR_INVALID;
+  return trace_impl(desc, w, args, m, x, x_final, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import metrics as M
 from .. import step as S
 
 
@@ -357,27 +358,36 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
 class TraceResult:
     """What ``trace()`` returns: ``x_final`` [B,C,H,W], ``frames`` [R,B,channels,H,W] (the state after
     each recorded step), ``steps`` (the R recorded step indices, counted from 1 within this call) and
-    ``attention`` [R,B,H,W] (the map of each recorded step) or None.  All detached."""
+    ``attention`` [R,B,H,W] (the map of each recorded step) or None; ``metrics``, an ``ImageMetrics``
+    of shape [R,B] (the state after each recorded step against ``target``) or None.  ``frames`` is
+    None for a trace with ``frames=False``.  All detached."""
 
-    __slots__ = ("x_final", "frames", "steps", "attention")
+    __slots__ = ("x_final", "frames", "steps", "attention", "metrics")
 
-    def __init__(self, x_final, frames, steps, attention):
+    def __init__(self, x_final, frames, steps, attention, metrics=None):
         self.x_final, self.frames, self.steps, self.attention = x_final, frames, steps, attention
+        self.metrics = metrics
 
     def __repr__(self):
-        return (f"TraceResult(steps={self.steps}, frames={tuple(self.frames.shape)}, "
-                f"attention={None if self.attention is None else tuple(self.attention.shape)})")
+        shape = lambda t: None if t is None else tuple(t.shape)
+        return (f"TraceResult(steps={self.steps}, frames={shape(self.frames)}, "
+                f"attention={shape(self.attention)}, "
+                f"metrics={None if self.metrics is None else shape(self.metrics.stacked)})")
 
 
 def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, every=1, record=None,
               channels=4, return_attention=False, fire_rate=1.0, message_gain=None, seed=None, sample_base=0,
-              first_step=0, offsets=None) -> TraceResult:
+              first_step=0, offsets=None, target=None, frames=True) -> TraceResult:
     """The shared body of ``NeuralCA.trace`` / ``NeuralCAGraph.trace``: a no-grad rollout that records
-    frames (and attention maps) in one native call."""
+    frames (and attention maps, and image metrics against ``target``) in one native call."""
     if x.dim() != 4:
         raise ValueError(f"state must be [B,C,H,W], got {tuple(x.shape)}")
     B, C, H, W = x.shape
     _check_norm(model)
+    if not isinstance(frames, bool):
+        raise ValueError(f"frames must be a bool, got {frames!r}")
+    if target is not None:
+        target = M.check_target(target, B, H, W)
     # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
     plan = S.build_trace(steps=steps, B=B, C=C, H=H, W=W, device=x.device, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
@@ -388,7 +398,15 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
         sched = plan.schedule
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
         desc.rng_step = plan.first_step
-        out, frames, attn = S.trace(desc, w, x, steps, sched.offsets or [], plan.record, plan.channels,
-                                    want_attention=plan.attention)
+        met = None
+        if target is None and frames:
+            out, frm, attn = S.trace(desc, w, x, steps, sched.offsets or [], plan.record, plan.channels,
+                                     want_attention=plan.attention)
+        else:
+            tgt, tbs = (None, 0) if target is None else M.device_target(target, x.device)
+            out, frm, attn, met = S.trace_metrics(desc, w, x, steps, sched.offsets or [], plan.record,
+                                                  plan.channels, tgt, tbs, want_attention=plan.attention,
+                                                  want_frames=frames)
+            met = None if met is None else M.ImageMetrics(met)
         del keep
-    return TraceResult(out, frames, list(plan.record), attn)
+    return TraceResult(out, frm, list(plan.record), attn, met)

@@ -97,7 +97,8 @@ class NeuralCAGraph(nn.Module):
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
-              sample_base: int = 0, first_step: int = 0, offsets=None) -> TraceResult:
+              sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
+              frames: bool = True) -> TraceResult:
         """``steps`` CA steps in one native call that also records (extension, not in the reference):
         the per-step Python loop of the regeneration diagnostic and the video generators, on the
         rollout pipeline.  Always runs under ``no_grad`` and returns detached tensors, whatever the
@@ -117,8 +118,15 @@ class NeuralCAGraph(nn.Module):
         ``trace(x_final, 3, seed=s, first_step=4)`` (and the matching offsets) continues one fire
         stream, so "grow, damage, regrow" is two calls.  ``offsets=None`` draws
         ``self.graph.sample_offsets()`` once per step in step order, as ``rollout()`` does.  Bad
-        arguments raise ``ValueError`` before anything is drawn or launched."""
+        arguments raise ``ValueError`` before anything is drawn or launched.
+
+        ``target`` (premultiplied RGBA, [4,H,W], [1,4,H,W] or [B,4,H,W]) also measures: the result's
+        ``metrics`` is an ``ImageMetrics`` (mse, pixel_perfect, psnr, ssim; ``metrics.py``) of shape
+        [R,B], the state after each recorded step against the target, bitwise
+        ``image_metrics(frames, target)``.  ``frames=False`` allocates and records no frames
+        (``result.frames`` is None): a regeneration curve is then [R,B,4] floats and nothing else."""
         return run_trace(self, x, steps, self.graph, self.hidden_only, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
                          message_gain=self.message_gain if message_gain is None else message_gain, seed=seed,
-                         sample_base=sample_base, first_step=first_step, offsets=offsets)
+                         sample_base=sample_base, first_step=first_step, offsets=offsets, target=target,
+                         frames=frames)

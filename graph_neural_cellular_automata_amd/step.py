@@ -539,6 +539,50 @@ def trace(desc, weights, x, steps: int, offsets_per_step: list, record: list, ch
     return out, frames, attn
 
 
+def trace_metrics(desc, weights, x, steps: int, offsets_per_step: list, record: list, channels: int,
+                  target, target_bstride: int, want_attention: bool = False, want_frames: bool = True):
+    """``trace`` that also measures (gnca_rollout_trace_metrics_f32): the image metrics of channels
+    0..3 of the state after each recorded step against ``target`` (a contiguous float32 device tensor
+    of premultiplied RGBA with sample stride ``target_bstride``, 0 = broadcast; None: nothing is
+    measured).  Returns ``(x_final, frames or None, attention or None, metrics [R,B,4] or None)``;
+    without ``want_frames`` no frame buffer is allocated."""
+    lib = L.load()
+    k = desc.num_offsets
+    flat = [v for offs in offsets_per_step for o in offs for v in o]
+    if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
+        raise ValueError("offsets_per_step must hold k pairs for every step")
+    arr = (ctypes.c_int8 * len(flat))(*flat) if flat else None
+    R = len(record)
+    rec = (ctypes.c_int32 * max(1, R))(*record)
+    out = torch.empty_like(x)
+    frames = None
+    if want_frames:
+        frames = torch.empty(R, desc.B, channels, desc.H, desc.W, dtype=torch.float32, device=x.device)
+    attn = torch.empty(R, desc.B, desc.H, desc.W, dtype=torch.float32, device=x.device) if want_attention else None
+    met = None if target is None else torch.empty(R, desc.B, 4, dtype=torch.float32, device=x.device)
+    a = L.TraceArgs()
+    a.steps, a.num_records, a.frame_channels, a.flags = int(steps), R, int(channels), 0
+    a.offsets = ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None
+    a.record = ctypes.cast(rec, ctypes.c_void_p)
+    a.frames = frames.data_ptr() if (frames is not None and R) else None
+    a.attn = attn.data_ptr() if (attn is not None and R) else None
+    m = L.TraceMetrics()
+    if met is not None:
+        # (R = 0: a placeholder element keeps both pointers set; nothing is written)
+        keep_out = met if R else torch.empty(4, dtype=torch.float32, device=x.device)
+        m.target, m.target_bstride, m.out = target.data_ptr(), int(target_bstride), keep_out.data_ptr()
+    n = lib.gnca_rollout_trace_metrics_workspace_bytes(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
+    if n == 0:
+        raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden}")
+    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    rc = lib.gnca_rollout_trace_metrics_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a),
+                                            ctypes.byref(m), x.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), stream_ptr(x.device))
+    L.check(rc, "gnca_rollout_trace_metrics_f32")
+    return out, frames, attn, met
+
+
 class RolloutCall:
     """A schedule bound to a descriptor: the C struct with its host arrays kept alive."""
 

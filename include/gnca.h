@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define GNCA_ABI_VERSION 4
+#define GNCA_ABI_VERSION 5
 #define GNCA_MAX_OFFSETS 128   /* >= (2r+1)^2-9 for r <= 5 (112) */
 
 /* gnca_step_desc.flags */
@@ -407,6 +407,53 @@ size_t gnca_rollout_trace_workspace_bytes(const gnca_step_desc* desc, const gnca
  */
 int gnca_rollout_trace_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
                            const float* x, float* x_final, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Image metrics on the device, and a recording rollout that measures.
+ * -------------------------------------------------------------------------------------------*/
+
+/*
+ * The trainers' per-iteration quality figures (src/training/train_graph_augmented_nca.py:405-422,
+ * skimage's structural_similarity / peak_signal_noise_ratio with their defaults), for every image of
+ * a batch: out[n*4 + {0,1,2,3}] = mse, pixel_perfect, psnr, ssim of image n.  Layouts as
+ * gnca_loss_premult_f32: pred [N,4,H,W] with sample stride pred_bstride floats and channel stride
+ * H*W, target premultiplied RGBA with sample stride target_bstride (0 = broadcast).
+ * With P = (pred_rgb * pred_alpha, pred_alpha) (the product rounded to fp32), T = target,
+ * X = clip(P_rgb, 0, 1), Y = clip(T_rgb, 0, 1):
+ *   mse            mean over 4 channels and all cells of (P - T)^2 (gnca_loss_premult_f32's value)
+ *   pixel_perfect  fraction of cells with |P_c - T_c| < 0.05 (fp32) in all 4 channels
+ *   psnr           10 log10(1 / mean((X - Y)^2)) over the 3 colour channels; +inf when the mean is 0
+ *   ssim           mean over the colour channels and all (H-6)(W-6) full 7x7 windows of
+ *                  (2 mx my + C1)(2 vxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)), window means m,
+ *                  sample (co)variances v = 49/48 (mxy - mx my), C1 = 1e-4, C2 = 9e-4;
+ *                  NaN when H < 7 or W < 7 (the other three are still computed)
+ * Everything after the fp32 premultiply and clip is fp64.  Fixed-order sums, no atomics: an image's
+ * four results are bitwise the same whatever N is and wherever the image stands in the batch.
+ * ws: >= gnca_image_metrics_workspace_bytes(N, H, W) bytes of device memory, 8-B aligned (may be
+ * NULL when that is 0).
+ */
+size_t gnca_image_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int gnca_image_metrics_f32(int32_t N, int32_t H, int32_t W, const float* pred, int64_t pred_bstride,
+                           const float* target, int64_t target_bstride, float* out, void* ws,
+                           size_t ws_bytes, void* stream);
+
+typedef struct gnca_trace_metrics {
+  const float* target;      /* DEVICE, premultiplied RGBA [4,H,W] or [B,4,H,W]                   */
+  int64_t target_bstride;   /* 0 = broadcast                                                     */
+  float* out;               /* DEVICE [R,B,4]: the metrics of the state after step record[r]     */
+} gnca_trace_metrics;
+
+/*
+ * gnca_rollout_trace_f32 that also measures: the same pieces, and at each record point the image
+ * metrics of channels 0..3 of the piece's output state (read in place) go to out[r].  args->frames
+ * may be NULL here (metrics without frames); args->attn as before.  The metrics are bitwise those of
+ * gnca_image_metrics_f32 on the recorded frames.  m->target and m->out both NULL: nothing is measured.
+ */
+size_t gnca_rollout_trace_metrics_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                                  const gnca_trace_metrics* m);
+int gnca_rollout_trace_metrics_f32(const gnca_step_desc* desc, const gnca_weights* w,
+                                   const gnca_trace_args* args, const gnca_trace_metrics* m, const float* x,
+                                   float* x_final, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Step-adjacent batch op: damage (src/utils/damage.py:15-138).  ONE damage kind for the whole
