@@ -90,6 +90,13 @@ class DamageDesc(ctypes.Structure):
                 ("alpha_thr", ctypes.c_float), ("softness", ctypes.c_float), ("sigma", ctypes.c_float)]
 
 
+class MaskedLossDesc(ctypes.Structure):
+    """Mirror of gnca_masked_loss_desc (include/gnca.h)."""
+    _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("alpha_thr", ctypes.c_float), ("lam_area", ctypes.c_float), ("lam_bg_alpha", ctypes.c_float),
+                ("lam_bg_rgb", ctypes.c_float), ("close_thresh", ctypes.c_float), ("close_steps", ctypes.c_int32)]
+
+
 DMG_SQUARE, DMG_CIRCLE, DMG_STRIPE_H, DMG_STRIPE_V = 0, 1, 2, 3
 DMG_ALPHA_DROP, DMG_ALPHA_DROP_SOFT, DMG_SALT_PEPPER, DMG_GAUSSIAN, DMG_HIDDEN_NOISE = 4, 5, 6, 7, 8
 
@@ -103,7 +110,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_fwd_f32", "gnca_rollout_bwd_f32", "gnca_attention_workspace_bytes",
            "gnca_attention_f32", "gnca_rollout_trace_workspace_bytes", "gnca_rollout_trace_f32",
            "gnca_image_metrics_workspace_bytes", "gnca_image_metrics_f32",
-           "gnca_rollout_trace_metrics_workspace_bytes", "gnca_rollout_trace_metrics_f32")
+           "gnca_rollout_trace_metrics_workspace_bytes", "gnca_rollout_trace_metrics_f32",
+           "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
+           "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -212,6 +221,18 @@ def load(path: str = LIB_PATH):
         lib.gnca_rollout_trace_metrics_f32.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                        ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics),
                                                        vp, vp, vp, sz, vp]
+        if hasattr(lib, "gnca_loss_masked_f32"):   # (a version-5 library from before these additions lacks them)
+            md = ctypes.POINTER(MaskedLossDesc)
+            lib.gnca_loss_masked_f32.restype = ctypes.c_int
+            lib.gnca_loss_masked_f32.argtypes = [md, vp, i64, vp, i64, vp, vp, vp, vp]
+            lib.gnca_loss_masked_bwd_f32.restype = ctypes.c_int
+            lib.gnca_loss_masked_bwd_f32.argtypes = [md, vp, i64, vp, i64, vp, vp, vp, i64, vp]
+            lib.gnca_loss_stability_workspace_bytes.restype = sz
+            lib.gnca_loss_stability_workspace_bytes.argtypes = [i32]
+            lib.gnca_loss_stability_f32.restype = ctypes.c_int
+            lib.gnca_loss_stability_f32.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, sz, vp]
+            lib.gnca_loss_stability_bwd_f32.restype = ctypes.c_int
+            lib.gnca_loss_stability_bwd_f32.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -1,6 +1,7 @@
 // gnca_aux.hip — step-adjacent batch ops of the rollout/training loop:
 // the damage curriculum (reference: src/utils/damage.py:15-138), one launch for the whole batch,
-// the premultiplied-RGBA loss and the image metrics (mse, pixel-perfect, psnr, ssim).
+// the premultiplied-RGBA loss, the classic trainer's target-masked loss and stability loss, and the
+// image metrics (mse, pixel-perfect, psnr, ssim).
 //
 // The reference loops over samples on the host, drawing each sample's position with a separate
 // torch.randint(...).item()-style call (a device sync per sample on GPU) and applying a masked
@@ -127,6 +128,146 @@ __global__ __launch_bounds__(kThreads) void gnca_loss_bwd(int B, int H, int W, c
       ga = fmaf(r, x, ga);
     }
     o[3 * HW + q] = s * ga;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The classic trainer's objective (train_intermediate_loss.py:37-51 and :256-267, with the graph
+// trainer's two background penalties, train_graph_augmented_nca.py:30-49): MSE over the cells where
+// the TARGET is alive plus three penalties, and the stability phase's MSE over the close samples.
+// Both read 8 planes once (traffic- and latency-bound); every sum is a fixed-order fp64 sum (per
+// thread, xor-shuffle, waves in order), so a sample's value does not depend on the batch around it.
+// ---------------------------------------------------------------------------------------------
+
+// the sum of `v` over the workgroup, in a fixed order, in every thread (red: one slot per wave)
+__device__ inline double block_sum(double v, double* red) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();   // (red may still be read from the previous sum)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+  return s;
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_masked_loss_fwd(const gnca_masked_loss_desc d, const float* pred,
+                                                                 long pbs, const float* tgt, long tbs, float* out,
+                                                                 int32_t* alive_count, int32_t* nsteps_out) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const size_t HW = (size_t)d.H * d.W;
+  const float* p = pred + (size_t)b * pbs;
+  const float* t = tgt + (size_t)b * tbs;
+  double prim = 0.0, bga = 0.0, bgrgb = 0.0, area = 0.0, cnt = 0.0;
+  for (size_t e = tid; e < HW; e += kThreads) {
+    const float ta = t[3 * HW + e], pa = p[3 * HW + e];
+    const bool alive = ta > d.alpha_thr;
+    area += (double)pa;
+    if (alive) {
+      cnt += 1.0;
+      const float ra = pa - ta;
+      prim += (double)(ra * ra);
+      for (int c = 0; c < 3; ++c) {
+        const float r = p[c * HW + e] - t[c * HW + e];   // the reference's fp32 difference, then its square
+        prim += (double)(r * r);
+      }
+    } else {
+      bga += (double)pa;
+      for (int c = 0; c < 3; ++c) bgrgb += (double)fabsf(p[c * HW + e]);
+    }
+  }
+  prim = block_sum(prim, red);
+  bga = block_sum(bga, red);
+  bgrgb = block_sum(bgrgb, red);
+  area = block_sum(area, red);
+  cnt = block_sum(cnt, red);   // (integers below 2^53: exact)
+  if (tid == 0) {
+    const double hw = (double)HW;
+    const double v = prim / (cnt + 1e-8) + (double)d.lam_bg_alpha * bga / hw +
+                     (double)d.lam_bg_rgb * bgrgb / (3.0 * hw) + (double)d.lam_area * area / hw;
+    const float vf = (float)v;
+    out[b] = vf;
+    alive_count[b] = (int32_t)cnt;
+    if (nsteps_out) nsteps_out[b] = vf < d.close_thresh ? d.close_steps : 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_masked_loss_bwd(const gnca_masked_loss_desc d, const float* pred,
+                                                                 long pbs, const float* tgt, long tbs,
+                                                                 const int32_t* alive_count, const float* g,
+                                                                 float* gp, long gbs) {
+  const size_t HW = (size_t)d.H * d.W, total = (size_t)d.B * HW;
+  const double hw = (double)HW;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
+    const size_t b = e / HW, q = e - b * HW;
+    const float* p = pred + b * pbs;
+    const float* t = tgt + b * tbs;
+    float* o = gp + b * gbs;
+    const double gb = (double)g[b];
+    const float s = (float)(2.0 * gb / ((double)alive_count[b] + 1e-8));   // (unused where nothing is alive)
+    const float ta = t[3 * HW + q], pa = p[3 * HW + q];
+    const bool alive = ta > d.alpha_thr;
+    const float pen_a = (float)(gb * ((alive ? 0.0 : (double)d.lam_bg_alpha) + (double)d.lam_area) / hw);
+    const float pen_c = alive ? 0.f : (float)(gb * (double)d.lam_bg_rgb / (3.0 * hw));
+    for (int c = 0; c < 3; ++c) {
+      const float x = p[c * HW + q];
+      const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);   // torch's abs gradient: sign(0) = 0
+      o[c * HW + q] = alive ? s * (x - t[c * HW + q]) : pen_c * sg;
+    }
+    o[3 * HW + q] = alive ? fmaf(s, pa - ta, pen_a) : pen_a;
+  }
+}
+
+// the stability phase: per-sample fp64 sums of the close samples (the others are not read) ...
+__global__ __launch_bounds__(kThreads) void gnca_stability_partial(int H, int W, const float* pred, long pbs,
+                                                                   const float* tgt, long tbs, const uint8_t* close,
+                                                                   double* part) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (!close[b]) {   // (uniform over the workgroup)
+    if (tid == 0) part[b] = 0.0;
+    return;
+  }
+  const size_t n = 4 * (size_t)H * W;
+  const float* p = pred + (size_t)b * pbs;
+  const float* t = tgt + (size_t)b * tbs;
+  double acc = 0.0;
+  for (size_t e = tid; e < n; e += kThreads) {
+    const double r = (double)(p[e] - t[e]);
+    acc = fma(r, r, acc);
+  }
+  acc = block_sum(acc, red);
+  if (tid == 0) part[b] = acc;
+}
+
+// ... then one workgroup adds them in a fixed order, counts the close samples and writes the scale
+__global__ __launch_bounds__(kThreads) void gnca_stability_finish(int B, int H, int W, const uint8_t* close,
+                                                                  const double* part, float* loss, float* scale) {
+  __shared__ double red[kThreads / 64];
+  double acc = 0.0, cnt = 0.0;
+  for (int b = threadIdx.x; b < B; b += kThreads)
+    if (close[b]) {
+      acc += part[b];
+      cnt += 1.0;
+    }
+  acc = block_sum(acc, red);
+  cnt = block_sum(cnt, red);
+  if (threadIdx.x == 0) {
+    const double sc = cnt > 0.0 ? 1.0 / (cnt * 4.0 * (double)H * (double)W) : 0.0;
+    loss[0] = (float)(acc * sc);
+    scale[0] = (float)sc;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_stability_bwd(int B, int H, int W, const float* pred, long pbs,
+                                                               const float* tgt, long tbs, const uint8_t* close,
+                                                               const float* scale, const float* g, float* gp,
+                                                               long gbs) {
+  const size_t n = 4 * (size_t)H * W, total = (size_t)B * n;
+  const float s = 2.f * g[0] * scale[0];
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
+    const size_t b = e / n, q = e - b * n;
+    gp[b * gbs + q] = close[b] ? s * (pred[b * pbs + q] - tgt[b * tbs + q]) : 0.f;
   }
 }
 
@@ -338,6 +479,78 @@ extern "C" int gnca_loss_premult_bwd_f32(int32_t B, int32_t H, int32_t W, const 
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(gnca_loss_bwd, dim3((unsigned)blocks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream),
                      B, H, W, pred, (long)pbs, target, (long)tbs, g, grad_pred, (long)gbs);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+static bool masked_desc_ok(const gnca_masked_loss_desc* d) { return d && d->B > 0 && d->H > 0 && d->W > 0; }
+
+// an elementwise launch's grid: one thread per element, grid-stride beyond 8192 workgroups
+static unsigned elementwise_blocks(size_t total) {
+  const size_t blocks = (total + kThreads - 1) / kThreads;
+  return (unsigned)(blocks > 8192 ? 8192 : blocks);
+}
+
+extern "C" int gnca_loss_masked_f32(const gnca_masked_loss_desc* d, const float* pred, int64_t pbs,
+                                    const float* target, int64_t tbs, float* per_sample, int32_t* alive_count,
+                                    int32_t* nsteps_out, void* stream) {
+  if (!masked_desc_ok(d) || !pred || !target || !per_sample || !alive_count || pbs < 0 || tbs < 0)
+    return GNCA_ERR_INVALID;
+  if (nsteps_out && d->close_steps < 0) return GNCA_ERR_INVALID;
+  hipLaunchKernelGGL(gnca_masked_loss_fwd, dim3(d->B), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), *d,
+                     pred, (long)pbs, target, (long)tbs, per_sample, alive_count, nsteps_out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+extern "C" int gnca_loss_masked_bwd_f32(const gnca_masked_loss_desc* d, const float* pred, int64_t pbs,
+                                        const float* target, int64_t tbs, const int32_t* alive_count,
+                                        const float* g, float* grad_pred, int64_t gbs, void* stream) {
+  if (!masked_desc_ok(d) || !pred || !target || !alive_count || !g || !grad_pred || pbs < 0 || tbs < 0 || gbs < 0)
+    return GNCA_ERR_INVALID;
+  hipLaunchKernelGGL(gnca_masked_loss_bwd, dim3(elementwise_blocks((size_t)d->B * d->H * d->W)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), *d, pred, (long)pbs, target, (long)tbs, alive_count, g,
+                     grad_pred, (long)gbs);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+extern "C" size_t gnca_loss_stability_workspace_bytes(int32_t B) {
+  return B > 0 ? (size_t)B * sizeof(double) : 0;
+}
+
+extern "C" int gnca_loss_stability_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pbs,
+                                       const float* target, int64_t tbs, const uint8_t* close, float* loss,
+                                       float* scale, void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || !pred || !target || !close || !loss || !scale || pbs < 0 || tbs < 0)
+    return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < gnca_loss_stability_workspace_bytes(B) || ((uintptr_t)ws & 7)) return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(ws);
+  hipLaunchKernelGGL(gnca_stability_partial, dim3(B), dim3(kThreads), 0, st, H, W, pred, (long)pbs, target,
+                     (long)tbs, close, part);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(gnca_stability_finish, dim3(1), dim3(kThreads), 0, st, B, H, W, close, part, loss, scale);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+extern "C" int gnca_loss_stability_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pbs,
+                                           const float* target, int64_t tbs, const uint8_t* close,
+                                           const float* scale, const float* g, float* grad_pred, int64_t gbs,
+                                           void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || !pred || !target || !close || !scale || !g || !grad_pred || pbs < 0 ||
+      tbs < 0 || gbs < 0)
+    return GNCA_ERR_INVALID;
+  hipLaunchKernelGGL(gnca_stability_bwd, dim3(elementwise_blocks((size_t)B * 4 * H * W)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), B, H, W, pred, (long)pbs, target, (long)tbs, close, scale,
+                     g, grad_pred, (long)gbs);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
   return GNCA_OK;

@@ -32,6 +32,10 @@
  *                        NeuralCA.forward, i.e. the per-step part of the trainers'
  *                        loss.backward() (BPTT): src/training/train_graph_augmented_nca.py:369,
  *                        src/training/train_intermediate_loss.py (same loop)
+ *   gnca_loss_masked_f32     masked_loss, src/training/train_intermediate_loss.py:37-51 and
+ *                            src/training/train_graph_augmented_nca.py:30-49
+ *   gnca_loss_stability_f32  the stability phase's loss on the close samples,
+ *                            src/training/train_intermediate_loss.py:256-267
  */
 #ifndef GNCA_H
 #define GNCA_H
@@ -501,6 +505,61 @@ int gnca_loss_premult_f32(int32_t B, int32_t H, int32_t W, const float* pred, in
 int gnca_loss_premult_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pred_bstride,
                               const float* target, int64_t target_bstride, const float* g,
                               float* grad_pred, int64_t grad_bstride, void* stream);
+
+/*
+ * The classic trainer's objective (src/training/train_intermediate_loss.py:37-51, with the two
+ * background penalties of src/training/train_graph_augmented_nca.py:30-49), fused.  Layouts are
+ * those of gnca_loss_premult_f32, but pred is the RAW slice state[:, :4]: nothing is premultiplied.
+ *   alive(b,i,j)  = target[b,3,i,j] > alpha_thr            (fp32, strict), dead = 1 - alive
+ *   n_b           = number of alive cells of sample b      (written to alive_count[b])
+ *   per_sample[b] = sum_{c<4,i,j} alive (pred - target)^2 / (n_b + 1e-8)
+ *                 + lam_bg_alpha sum pred_a dead / HW
+ *                 + lam_bg_rgb   sum_{c<3} |pred_c dead| / (3 HW)
+ *                 + lam_area     sum pred_a / HW
+ * One workgroup per sample; fixed-order fp64 sums, so a sample's value is bitwise the same alone,
+ * in a batch and at any batch position.  With nsteps_out set, the stability phase's schedule is
+ * written too: nsteps_out[b] = per_sample[b] < close_thresh ? close_steps : 0, compared on the stored
+ * fp32 value (close_steps < 0 is GNCA_ERR_INVALID).  The backward writes all four channels of
+ * grad_pred = g[b] * d per_sample[b] / d pred, with sign(0) = 0 in the |.| term.
+ */
+typedef struct gnca_masked_loss_desc {
+  int32_t B, H, W;
+  float alpha_thr;      /* alive(b,i,j) = target[b,3,i,j] > alpha_thr, compared in fp32, strict */
+  float lam_area;       /* * mean_{i,j} pred_a                                                   */
+  float lam_bg_alpha;   /* * mean_{i,j} pred_a * dead                 (dead = 1 - alive)         */
+  float lam_bg_rgb;     /* * mean_{c<3,i,j} |pred_c * dead|                                      */
+  float close_thresh;   /* read only when nsteps_out != NULL                                     */
+  int32_t close_steps;  /* K                                                                     */
+} gnca_masked_loss_desc;
+
+int gnca_loss_masked_f32(const gnca_masked_loss_desc* d, const float* pred, int64_t pred_bstride,
+                         const float* target, int64_t target_bstride, float* per_sample /*[B]*/,
+                         int32_t* alive_count /*[B], out*/, int32_t* nsteps_out /*[B] or NULL*/,
+                         void* stream);
+int gnca_loss_masked_bwd_f32(const gnca_masked_loss_desc* d, const float* pred, int64_t pred_bstride,
+                             const float* target, int64_t target_bstride,
+                             const int32_t* alive_count, const float* g /*[B]*/,
+                             float* grad_pred, int64_t grad_bstride, void* stream);
+
+/*
+ * The stability phase's loss (src/training/train_intermediate_loss.py:256-267), without the host
+ * wait on close.any():
+ *   loss = scale * sum_{b: close[b] != 0} sum_{c<4,i,j} (pred - target)^2,
+ *   scale = 1 / (n_close 4 HW); no close sample: scale = 0 and loss = 0 (the reference skips the term).
+ * Samples that are not close are not read.  ws: >= gnca_loss_stability_workspace_bytes(B) bytes of
+ * device memory, 8-B aligned (else GNCA_ERR_WORKSPACE; the size is 0 on B <= 0).  Forward: per-sample
+ * fp64 partials, then a one-workgroup fixed-order finish that also writes `scale` for the backward:
+ *   grad_pred = g[0] * scale * 2 (pred - target) on close samples, 0 on the others.
+ */
+size_t gnca_loss_stability_workspace_bytes(int32_t B);
+int gnca_loss_stability_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pred_bstride,
+                            const float* target, int64_t target_bstride, const uint8_t* close /*[B]*/,
+                            float* loss /*[1]*/, float* scale /*[1], out*/, void* ws, size_t ws_bytes,
+                            void* stream);
+int gnca_loss_stability_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pred_bstride,
+                                const float* target, int64_t target_bstride, const uint8_t* close,
+                                const float* scale, const float* g /*[1]*/, float* grad_pred,
+                                int64_t grad_bstride, void* stream);
 
 #ifdef __cplusplus
 }
