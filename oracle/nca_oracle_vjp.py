@@ -89,7 +89,7 @@ def nca_step_vjp(x: np.ndarray, p: dict, cfg: dict, gy: np.ndarray, *, chosen=No
         Q, Kf, M = conv1x1(x, Wq, bq), conv1x1(x, Wk, bk), conv1x1(x, Wm, bm)
         qp = Q.mean(axis=(2, 3))
         a2a = cfg["alive_to_alive"]
-        A_send = alive_mask(x, cfg["alpha_thr"]) if a2a else None
+        A_send = alive_mask(x, cfg.get("graph_alpha_thr", cfg["alpha_thr"])) if a2a else None
         msgs, kps, sends = [], [], []
         for dy, dx in chosen:
             Ms = shift(M, dy, dx)
