@@ -16,6 +16,10 @@
  *   - Return value: 0 (GNCA_OK) or a negative gnca_status; gnca_status_string() names it.
  *   - Stateless and reentrant (gnca_rollout_f32's sub-batch streams are per-device helpers whose
  *     enqueue is serialised by an internal lock).
+ *   - The prior contents of `ws`, `tape` and every output buffer are ignored, and every output is
+ *     written completely, unless an entry point says otherwise (a continuation piece of
+ *     gnca_rollout_ex_f32 reads what the previous piece left in `ws`; `saved` and `tape` are read by
+ *     the backward that they are passed to).
  *
  * Reference interfaces replaced (paths relative to the reference root):
  *   gnca_step_f32        NeuralCAGraph.forward        src/modules/ncagraph.py:106-168
