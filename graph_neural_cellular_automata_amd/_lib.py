@@ -97,6 +97,34 @@ class MaskedLossDesc(ctypes.Structure):
                 ("lam_bg_rgb", ctypes.c_float), ("close_thresh", ctypes.c_float), ("close_steps", ctypes.c_int32)]
 
 
+OPTIM_MAX_TENSORS = 24
+OPTIM_ONE_LAUNCH_MAX = 65536   # elements a one-launch gnca_optim_step call may hold (include/gnca.h)
+OPTIM_POLICY_NONE, OPTIM_POLICY_NORMALIZE, OPTIM_POLICY_CLIP = 0, 1, 2
+OPTIM_SUMSQ, OPTIM_UPDATE = 1, 2
+
+
+class OptimTensor(ctypes.Structure):
+    """Mirror of gnca_optim_tensor (include/gnca.h): device pointers and the host-computed knobs."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("bias1", ctypes.c_double), ("bias2", ctypes.c_double)]
+
+
+class OptimDesc(ctypes.Structure):
+    """Mirror of gnca_optim_desc (include/gnca.h): passed by value to the kernels."""
+    _fields_ = [("policy", ctypes.c_int32), ("num_tensors", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("sumsq_base", ctypes.c_int32), ("sumsq_count", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("sumsq", ctypes.c_void_p), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("max_norm", ctypes.c_double), ("norm_eps", ctypes.c_double),
+                ("t", OptimTensor * OPTIM_MAX_TENSORS)]
+
+
+class PoolCommitDesc(ctypes.Structure):
+    """Mirror of gnca_pool_commit_desc (include/gnca.h)."""
+    _fields_ = [("pool_slots", ctypes.c_int64), ("sample_elems", ctypes.c_int64), ("B", ctypes.c_int32),
+                ("n_reset", ctypes.c_int32)]
+
+
 DMG_SQUARE, DMG_CIRCLE, DMG_STRIPE_H, DMG_STRIPE_V = 0, 1, 2, 3
 DMG_ALPHA_DROP, DMG_ALPHA_DROP_SOFT, DMG_SALT_PEPPER, DMG_GAUSSIAN, DMG_HIDDEN_NOISE = 4, 5, 6, 7, 8
 
@@ -112,7 +140,7 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_image_metrics_workspace_bytes", "gnca_image_metrics_f32",
            "gnca_rollout_trace_metrics_workspace_bytes", "gnca_rollout_trace_metrics_f32",
            "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
-           "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32")
+           "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -233,6 +261,11 @@ def load(path: str = LIB_PATH):
             lib.gnca_loss_stability_f32.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, sz, vp]
             lib.gnca_loss_stability_bwd_f32.restype = ctypes.c_int
             lib.gnca_loss_stability_bwd_f32.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]
+        if hasattr(lib, "gnca_optim_step"):   # (likewise: loss._entry-style callers name what is missing)
+            lib.gnca_optim_step.restype = ctypes.c_int
+            lib.gnca_optim_step.argtypes = [ctypes.POINTER(OptimDesc), vp]
+            lib.gnca_pool_commit.restype = ctypes.c_int
+            lib.gnca_pool_commit.argtypes = [ctypes.POINTER(PoolCommitDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

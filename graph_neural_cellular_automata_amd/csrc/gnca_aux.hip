@@ -455,10 +455,230 @@ int met_bands(int32_t N, int32_t H) {
   return nb * (long)N > 0x7fffffffL ? 0 : (int)nb;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The iteration's tail (train_graph_augmented_nca.py:367-391, train_intermediate_loss.py:269-296):
+// gradient policy + Adam over a by-value table of tensors, and the pool write-back.  Both move a few
+// tens of KB: what counts is one launch, no host wait and a fixed summation order.
+// ---------------------------------------------------------------------------------------------
+constexpr int kOptChunk = 2048;      // elements per update workgroup: two float4 per thread
+constexpr int kCommitChunk = 4096;   // floats per copy workgroup: four float4 per thread
+
+// the sum of squares of g[0 .. n), in every thread: thread t adds the quads t, t + kThreads, ...
+// element by element, then element 4 (n / 4) + t of the tail, then block_sum.  The order depends on
+// n alone: a 16-byte-aligned g is read with float4 loads, any other with scalar loads of the same
+// elements in the same order (the squares are exact in fp64, so the bits agree).
+__device__ inline double tensor_sumsq(const float* g, int64_t n, double* red) {
+  const int tid = threadIdx.x;
+  const int64_t nq = n >> 2;
+  double acc = 0.0;
+  if (((uintptr_t)g & 15) == 0) {
+    for (int64_t q = tid; q < nq; q += kThreads) {
+      const f4 x = *reinterpret_cast<const f4*>(g + 4 * q);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc += (double)x[k] * (double)x[k];
+    }
+  } else {
+    for (int64_t q = tid; q < nq; q += kThreads)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc += (double)g[4 * q + k] * (double)g[4 * q + k];
+  }
+  if (tid < (int)(n & 3)) acc += (double)g[4 * nq + tid] * (double)g[4 * nq + tid];
+  return block_sum(acc, red);
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_optim_sumsq(const gnca_optim_desc d) {
+  __shared__ double red[kThreads / 64];
+  const int i = blockIdx.x;
+  const double s = tensor_sumsq(d.t[i].g, d.t[i].numel, red);
+  if (threadIdx.x == 0) d.sumsq[d.sumsq_base + i] = s;
+}
+
+// torch's Adam, one element (torch/optim/adam.py:_single_tensor_adam and the pointwise kernels it
+// calls: add(alpha), lerp, mul + addcmul, sqrt / bias + eps, addcdiv), after the gradient policy
+struct OptimConsts {
+  bool normalize;   // g / div (the tensor's norm + norm_eps)
+  float div, mul;   // mul: the clip coefficient (1 for the other policies)
+  float wd, w1, b2, w2, bc2s, eps, nstep;
+};
+
+__device__ __forceinline__ void adam_element(const OptimConsts& k, float g, float& p, float& m, float& v) {
+  if (k.normalize) g = g / k.div;
+  g = g * k.mul;
+  if (k.wd != 0.f) g = g + k.wd * p;
+  const float diff = g - m;
+  m = k.w1 < 0.5f ? m + k.w1 * diff : g - diff * (1.f - k.w1);
+  v = v * k.b2 + (k.w2 * g) * g;
+  const float den = sqrtf(v) / k.bc2s + k.eps;
+  p = p + (k.nstep * m) / den;
+}
+
+// one workgroup per kOptChunk elements of one tensor
+__global__ __launch_bounds__(kThreads) void gnca_optim_update(const gnca_optim_desc d) {
+  __shared__ double red[kThreads / 64];
+  int i = 0;
+  int64_t c = blockIdx.x;
+  for (; i < d.num_tensors; ++i) {   // (uniform over the workgroup)
+    const int64_t nc = (d.t[i].numel + kOptChunk - 1) / kOptChunk;
+    if (c < nc) break;
+    c -= nc;
+  }
+  if (i >= d.num_tensors) return;
+  const gnca_optim_tensor t = d.t[i];
+  OptimConsts k;
+  k.normalize = d.policy == GNCA_OPTIM_POLICY_NORMALIZE;
+  k.div = 1.f;
+  k.mul = 1.f;
+  if (k.normalize) {
+    const double ss = d.sumsq ? d.sumsq[d.sumsq_base + i] : tensor_sumsq(t.g, t.numel, red);
+    k.div = (float)sqrt(ss) + (float)d.norm_eps;
+  } else if (d.policy == GNCA_OPTIM_POLICY_CLIP) {
+    double tot = 0.0;
+    if (d.sumsq) {
+      for (int j = 0; j < d.sumsq_count; ++j) tot += d.sumsq[j];
+    } else {
+      for (int j = 0; j < d.num_tensors; ++j) tot += tensor_sumsq(d.t[j].g, d.t[j].numel, red);
+    }
+    const float coef = (float)d.max_norm / ((float)sqrt(tot) + 1e-6f);
+    k.mul = coef > 1.f ? 1.f : coef;   // (a NaN norm stays NaN, as torch.clamp leaves it)
+  }
+  k.wd = (float)t.weight_decay;
+  k.w1 = (float)(1.0 - d.beta1);
+  k.b2 = (float)d.beta2;
+  k.w2 = (float)(1.0 - d.beta2);
+  k.bc2s = (float)sqrt(t.bias2);
+  k.eps = (float)d.eps;
+  k.nstep = (float)(-(t.lr / t.bias1));
+  const int tid = threadIdx.x;
+  const int64_t e0 = c * kOptChunk;
+  const int64_t n = t.numel - e0 < kOptChunk ? t.numel - e0 : kOptChunk;   // this chunk's elements
+  float* p = t.p + e0;
+  const float* g = t.g + e0;
+  float* m = t.m + e0;
+  float* v = t.v + e0;
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+  const int64_t nv = vec ? (n & ~(int64_t)3) : 0;   // elements done with 16-byte accesses
+  for (int64_t e = 4 * (int64_t)tid; e < nv; e += 4 * kThreads) {
+    const f4 gv = *reinterpret_cast<const f4*>(g + e);
+    f4 pv = *reinterpret_cast<f4*>(p + e), mv = *reinterpret_cast<f4*>(m + e), vv = *reinterpret_cast<f4*>(v + e);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float pe = pv[q], me = mv[q], ve = vv[q];
+      adam_element(k, gv[q], pe, me, ve);
+      pv[q] = pe; mv[q] = me; vv[q] = ve;
+    }
+    *reinterpret_cast<f4*>(p + e) = pv;
+    *reinterpret_cast<f4*>(m + e) = mv;
+    *reinterpret_cast<f4*>(v + e) = vv;
+  }
+  for (int64_t e = nv + tid; e < n; e += kThreads) adam_element(k, g[e], p[e], m[e], v[e]);
+}
+
+// does loss `o` of sample j rank before loss `mine` of sample b (torch.topk's descending order, a
+// NaN above every number; ties and NaNs among themselves by lower index)?
+__device__ __forceinline__ bool ranks_before(float o, int j, float mine, int b) {
+  const bool on = o != o, mn = mine != mine;
+  if (on != mn) return on;
+  if (on || o == mine) return j < b;
+  return o > mine;
+}
+
+// one workgroup per (sample, kCommitChunk floats): each ranks its own sample, picks its source and
+// copies its chunk into the sample's slot
+__global__ __launch_bounds__(kThreads) void gnca_pool_commit_copy(const gnca_pool_commit_desc d, int chunks,
+                                                                  float* pool, const int64_t* slots,
+                                                                  const float* state, const float* per,
+                                                                  const float* seeds, const float* seed1,
+                                                                  const int64_t* rand_idx) {
+  __shared__ int cnt[kThreads / 64];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / chunks, c = blockIdx.x - b * chunks;
+  const int64_t E = d.sample_elems;
+  const int64_t slot = slots[b];
+  if (slot < 0 || slot >= d.pool_slots) return;   // (uniform over the workgroup)
+  const float* src = state + (int64_t)b * E;
+  if (rand_idx != nullptr && *rand_idx == (int64_t)b) {
+    src = seed1;
+  } else if (d.n_reset > 0) {
+    const float mine = per[b];
+    int r = 0;
+    for (int j = tid; j < d.B; j += kThreads) r += ranks_before(per[j], j, mine, b) ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off);
+    if ((tid & 63) == 0) cnt[tid >> 6] = r;
+    __syncthreads();
+    r = 0;
+    for (int w = 0; w < kThreads / 64; ++w) r += cnt[w];
+    if (r < d.n_reset) src = seeds + (int64_t)r * E;
+  }
+  const int64_t e0 = (int64_t)c * kCommitChunk;
+  const int64_t n = E - e0 < kCommitChunk ? E - e0 : kCommitChunk;
+  src += e0;
+  float* dst = pool + slot * E + e0;
+  const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const int64_t nv = vec ? (n & ~(int64_t)3) : 0;
+  for (int64_t e = 4 * (int64_t)tid; e < nv; e += 4 * kThreads)
+    *reinterpret_cast<f4*>(dst + e) = *reinterpret_cast<const f4*>(src + e);
+  for (int64_t e = nv + tid; e < n; e += kThreads) dst[e] = src[e];
+}
+
 }  // namespace
 }  // namespace gnca
 
 using namespace gnca;
+
+extern "C" int gnca_optim_step(const gnca_optim_desc* d, void* stream) {
+  if (!d || d->num_tensors < 0 || d->num_tensors > GNCA_OPTIM_MAX_TENSORS) return GNCA_ERR_INVALID;
+  if (d->policy < GNCA_OPTIM_POLICY_NONE || d->policy > GNCA_OPTIM_POLICY_CLIP) return GNCA_ERR_INVALID;
+  if (d->flags & ~(GNCA_OPTIM_SUMSQ | GNCA_OPTIM_UPDATE)) return GNCA_ERR_INVALID;
+  int64_t chunks = 0, elems = 0;
+  for (int i = 0; i < d->num_tensors; ++i) {
+    const gnca_optim_tensor& t = d->t[i];
+    if (!t.p || !t.g || !t.m || !t.v || t.numel < 0) return GNCA_ERR_INVALID;
+    chunks += (t.numel + kOptChunk - 1) / kOptChunk;
+    elems += t.numel;
+    if (chunks > 0x7fffffffLL) return GNCA_ERR_INVALID;
+  }
+  const bool sums = d->policy != GNCA_OPTIM_POLICY_NONE;
+  if (sums && d->sumsq) {
+    if (((uintptr_t)d->sumsq & 7) || d->sumsq_base < 0 || d->sumsq_count < 0 ||
+        (int64_t)d->sumsq_base + d->num_tensors > (int64_t)d->sumsq_count)
+      return GNCA_ERR_WORKSPACE;
+  } else if (sums) {
+    if (d->flags != 0) return GNCA_ERR_INVALID;
+    if (elems > GNCA_OPTIM_ONE_LAUNCH_MAX) return GNCA_ERR_WORKSPACE;
+  }
+  if (d->num_tensors == 0) return GNCA_OK;
+  const uint32_t flags = (sums && d->sumsq && d->flags) ? d->flags : (GNCA_OPTIM_SUMSQ | GNCA_OPTIM_UPDATE);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e = hipSuccess;
+  if (sums && d->sumsq && (flags & GNCA_OPTIM_SUMSQ)) {
+    hipLaunchKernelGGL(gnca_optim_sumsq, dim3((unsigned)d->num_tensors), dim3(kThreads), 0, st, *d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && (flags & GNCA_OPTIM_UPDATE) && chunks > 0) {
+    hipLaunchKernelGGL(gnca_optim_update, dim3((unsigned)chunks), dim3(kThreads), 0, st, *d);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+extern "C" int gnca_pool_commit(const gnca_pool_commit_desc* d, float* pool, const int64_t* slots,
+                                const float* state, const float* per_sample, const float* seeds,
+                                const float* seed1, const int64_t* rand_idx, void* stream) {
+  if (!d || d->B <= 0 || d->sample_elems <= 0 || d->pool_slots <= 0 || d->n_reset < 0 || d->n_reset > d->B)
+    return GNCA_ERR_INVALID;
+  if (!pool || !slots || !state) return GNCA_ERR_INVALID;
+  if (d->n_reset > 0 && (!per_sample || !seeds)) return GNCA_ERR_INVALID;
+  if ((rand_idx != nullptr) != (seed1 != nullptr)) return GNCA_ERR_INVALID;
+  const int64_t chunks = (d->sample_elems + kCommitChunk - 1) / kCommitChunk;
+  if (chunks * d->B > 0x7fffffffLL) return GNCA_ERR_INVALID;
+  hipLaunchKernelGGL(gnca_pool_commit_copy, dim3((unsigned)(chunks * d->B)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), *d, (int)chunks, pool, slots, state, per_sample, seeds,
+                     seed1, rand_idx);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
 
 extern "C" int gnca_loss_premult_f32(int32_t B, int32_t H, int32_t W, const float* pred, int64_t pbs,
                                      const float* target, int64_t tbs, float* per_sample, void* stream) {

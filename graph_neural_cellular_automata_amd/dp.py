@@ -61,14 +61,20 @@ def clip_gradients_(params, max_norm: float = 0.5) -> torch.Tensor:
     return torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], max_norm)
 
 
+def keep_gradients_(params) -> None:
+    """The "none" policy: the gradients stay as the all-reduce left them."""
+
+
 # the trainers' gradient policies, applied after the all-reduce
 POLICIES = {"normalize": normalize_gradients_,        # train_graph_augmented_nca.py:371-373
-            "clip": clip_gradients_}                  # train_intermediate_loss.py:282
+            "clip": clip_gradients_,                  # train_intermediate_loss.py:282
+            "none": keep_gradients_}                  # the optimiser applies its own (optim.FusedAdam)
 
 
 def train_step(model, optimizer, loss, group=None, policy: str = "normalize") -> None:
     """backward -> flat all-reduce -> the trainer's gradient policy -> optimizer step.
-    ``policy``: "normalize" (graph trainer) or "clip" (classic trainer, max norm 0.5)."""
+    ``policy``: "normalize" (graph trainer), "clip" (classic trainer, max norm 0.5) or "none": the way
+    to use an ``optim.FusedAdam`` that carries its own ``grad_policy`` (policy and Adam in one launch)."""
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     params = [p for p in model.parameters() if p.requires_grad]

@@ -40,6 +40,12 @@
  *                            src/training/train_graph_augmented_nca.py:30-49
  *   gnca_loss_stability_f32  the stability phase's loss on the close samples,
  *                            src/training/train_intermediate_loss.py:256-267
+ *   gnca_optim_step          the gradient policy and optimizer.step(),
+ *                            src/training/train_graph_augmented_nca.py:367-375 and
+ *                            src/training/train_intermediate_loss.py:280-283
+ *   gnca_pool_commit         the pool write-back with worst-k reset and random reseed,
+ *                            src/training/train_graph_augmented_nca.py:377-391 and
+ *                            src/training/train_intermediate_loss.py:269-296
  */
 #ifndef GNCA_H
 #define GNCA_H
@@ -564,6 +570,96 @@ int gnca_loss_stability_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pr
                                 const float* target, int64_t target_bstride, const uint8_t* close,
                                 const float* scale, const float* g /*[1]*/, float* grad_pred,
                                 int64_t grad_bstride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The iteration's tail: gradient policy + Adam in one call, and the pool write-back in one call.
+ * Neither name carries the _f32 suffix of the entry points above.
+ * -------------------------------------------------------------------------------------------*/
+
+/*
+ * gnca_optim_step: the trainers' gradient policy followed by torch.optim.Adam's update (no amsgrad,
+ * L2 weight decay), for up to GNCA_OPTIM_MAX_TENSORS tensors per call
+ * (src/training/train_graph_augmented_nca.py:367-375, src/training/train_intermediate_loss.py:280-283).
+ * Per tensor, in fp32 and in torch's order of operations:
+ *   NORMALIZE  g <- g / (||g||_2 + norm_eps)                       (the tensor's own norm)
+ *   CLIP       g <- g * min(max_norm / (total + 1e-6), 1),  total = 2-norm over ALL tensors
+ *   g <- g + weight_decay p
+ *   m <- m + (1 - beta1)(g - m)          v <- beta2 v + (1 - beta2) g g
+ *   p <- p - (lr / bias1) m / (sqrt(v) / sqrt(bias2) + eps)
+ * with bias1 = 1 - beta1^t and bias2 = 1 - beta2^t computed by the caller from the tensor's own step
+ * count t.  g is read, never written.  The sums of squares are fp64, in a fixed order that depends on
+ * the element count alone (not on the pointer's alignment): bitwise reproducible, no atomics.
+ *
+ * sumsq == NULL: one launch.  Every workgroup recomputes the sums it needs (NORMALIZE: its tensor's,
+ * CLIP: every tensor's of this call, which must then be all of them).  Allowed while the call's
+ * tensors hold at most GNCA_OPTIM_ONE_LAUNCH_MAX elements together (else GNCA_ERR_WORKSPACE).
+ * sumsq != NULL: device memory, fp64 [sumsq_count], 8-B aligned; tensor i of this call owns
+ * sumsq[sumsq_base + i].  GNCA_OPTIM_SUMSQ writes those (one launch, one workgroup per tensor),
+ * GNCA_OPTIM_UPDATE then updates from them (one launch; CLIP adds sumsq[0 .. sumsq_count) in index
+ * order, so several calls' tensors can share one total).  flags = 0 means both, in that order.
+ * POLICY_NONE is always one launch and ignores sumsq.  The whole descriptor travels as the kernel
+ * argument: nothing is copied to the device and no table lives in device memory.
+ */
+#define GNCA_OPTIM_MAX_TENSORS 24
+#define GNCA_OPTIM_ONE_LAUNCH_MAX 65536   /* elements; 256 KB of gradient re-read from L2 per workgroup */
+#define GNCA_OPTIM_POLICY_NONE      0
+#define GNCA_OPTIM_POLICY_NORMALIZE 1
+#define GNCA_OPTIM_POLICY_CLIP      2
+#define GNCA_OPTIM_SUMSQ  (1u << 0)
+#define GNCA_OPTIM_UPDATE (1u << 1)
+
+typedef struct gnca_optim_tensor {
+  float* p;             /* DEVICE, contiguous fp32 [numel]: the parameter, updated in place          */
+  const float* g;       /* its gradient (read only)                                                  */
+  float* m;             /* exp_avg                                                                   */
+  float* v;             /* exp_avg_sq                                                                */
+  int64_t numel;
+  double lr;
+  double weight_decay;
+  double bias1;         /* 1 - beta1^t                                                               */
+  double bias2;         /* 1 - beta2^t                                                               */
+} gnca_optim_tensor;
+
+typedef struct gnca_optim_desc {
+  int32_t policy;       /* GNCA_OPTIM_POLICY_*                                                       */
+  int32_t num_tensors;  /* 0 .. GNCA_OPTIM_MAX_TENSORS (0: nothing is launched)                      */
+  uint32_t flags;       /* GNCA_OPTIM_SUMSQ / GNCA_OPTIM_UPDATE with sumsq; 0 = both                  */
+  int32_t sumsq_base;
+  int32_t sumsq_count;
+  int32_t reserved;     /* 0                                                                         */
+  double* sumsq;        /* DEVICE fp64 [sumsq_count] or NULL                                         */
+  double beta1, beta2, eps;
+  double max_norm;      /* CLIP                                                                      */
+  double norm_eps;      /* NORMALIZE (the trainers' 1e-8)                                            */
+  gnca_optim_tensor t[GNCA_OPTIM_MAX_TENSORS];
+} gnca_optim_desc;
+
+int gnca_optim_step(const gnca_optim_desc* desc, void* stream);
+
+/*
+ * gnca_pool_commit: the trainers' pool write-back with worst-k reset and random reseed
+ * (src/training/train_graph_augmented_nca.py:377-391, src/training/train_intermediate_loss.py:269-296)
+ * in one launch, with no clone of the batch and no host wait.  For every b < B it writes the
+ * sample_elems floats of pool slot slots[b] (slots: distinct, each in 0 .. pool_slots-1; a slot
+ * outside that range is skipped) from
+ *   seed1                   where rand_idx != NULL and *rand_idx == b (applied last: it wins),
+ *   seeds + r sample_elems  where r < n_reset, r = sample b's rank by descending per_sample,
+ *   state + b sample_elems  otherwise.
+ * Rank 0 is the worst (largest) loss, as torch.topk orders; a NaN ranks above every number; equal
+ * losses (and NaNs among themselves) rank by lower b first.  Only the B addressed slots are
+ * written.  per_sample [B] and seeds [n_reset, sample_elems] may be NULL when n_reset == 0; seed1
+ * [sample_elems] and rand_idx (one int64 on the device) may be NULL together (no reseed).
+ */
+typedef struct gnca_pool_commit_desc {
+  int64_t pool_slots;    /* P                                                                        */
+  int64_t sample_elems;  /* C*H*W                                                                    */
+  int32_t B;
+  int32_t n_reset;       /* 0 .. B                                                                   */
+} gnca_pool_commit_desc;
+
+int gnca_pool_commit(const gnca_pool_commit_desc* desc, float* pool, const int64_t* slots,
+                     const float* state, const float* per_sample, const float* seeds, const float* seed1,
+                     const int64_t* rand_idx, void* stream);
 
 #ifdef __cplusplus
 }
