@@ -83,6 +83,14 @@ class TraceMetrics(ctypes.Structure):
     _fields_ = [("target", ctypes.c_void_p), ("target_bstride", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
+DIAG_FIELDS = ("magnitude", "groups", "per_offset", "raw", "attention", "sender_union", "receiver", "weights")
+
+
+class GraphDiagOut(ctypes.Structure):
+    """Mirror of gnca_graph_diag_out (include/gnca.h): device output pointers, NULL = skipped."""
+    _fields_ = [(n, ctypes.c_void_p) for n in DIAG_FIELDS]
+
+
 class DamageDesc(ctypes.Structure):
     """Mirror of gnca_damage_desc (include/gnca.h)."""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -140,7 +148,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_image_metrics_workspace_bytes", "gnca_image_metrics_f32",
            "gnca_rollout_trace_metrics_workspace_bytes", "gnca_rollout_trace_metrics_f32",
            "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
-           "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit")
+           "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit",
+           "gnca_graph_diag_workspace_bytes", "gnca_graph_diag", "gnca_rollout_trace_diag_workspace_bytes",
+           "gnca_rollout_trace_diag")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -266,6 +276,19 @@ def load(path: str = LIB_PATH):
             lib.gnca_optim_step.argtypes = [ctypes.POINTER(OptimDesc), vp]
             lib.gnca_pool_commit.restype = ctypes.c_int
             lib.gnca_pool_commit.argtypes = [ctypes.POINTER(PoolCommitDesc), vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(lib, "gnca_graph_diag"):   # (likewise)
+            do = ctypes.POINTER(GraphDiagOut)
+            lib.gnca_graph_diag_workspace_bytes.restype = sz
+            lib.gnca_graph_diag_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc)]
+            lib.gnca_graph_diag.restype = ctypes.c_int
+            lib.gnca_graph_diag.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights), vp, do, vp, sz, vp]
+            lib.gnca_rollout_trace_diag_workspace_bytes.restype = sz
+            lib.gnca_rollout_trace_diag_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(TraceArgs),
+                                                                    ctypes.POINTER(TraceMetrics)]
+            lib.gnca_rollout_trace_diag.restype = ctypes.c_int
+            lib.gnca_rollout_trace_diag.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                    ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics), do,
+                                                    vp, vp, vp, sz, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -2892,48 +2892,81 @@ static bool attn_layout(const gnca_step_desc* d, AttnLayout* L) {
   return true;
 }
 
-// S(p) for every cell: CP = the channel count rounded up to 16 (registers hold the cell's channels)
+// W_M / b_M into LDS, zero-padded to CP (ends with the workgroup's barrier)
 template <int CP>
-__global__ __launch_bounds__(kThreads) void gnca_attn_sfield(const AttnArgs a) {
-  __shared__ float wms[CP * CP];
-  __shared__ float bms[CP];
-  const int C = a.C, H = a.H, W = a.W, HW = H * W;
+__device__ inline void attn_load_wm(const AttnArgs& a, float* wms, float* bms) {
+  const int C = a.C;
   for (int e = threadIdx.x; e < CP * CP; e += kThreads) {
     const int co = e / CP, ci = e - co * CP;
     wms[e] = (co < C && ci < C) ? a.wm[co * C + ci] : 0.f;
   }
   for (int e = threadIdx.x; e < CP; e += kThreads) bms[e] = e < C ? a.bm[e] : 0.f;
   __syncthreads();
+}
+
+// 3x3 max-pool of a sample's alpha plane at cell (i, j) with -inf padding: the window clamped at the
+// image edge repeats an in-window value (the same max)
+__device__ inline float attn_pooled_alpha(const float* al, int i, int j, int H, int W) {
+  const int r0 = (i > 0 ? i - 1 : i) * W, r1 = i * W, r2 = (i < H - 1 ? i + 1 : i) * W;
+  const int c0 = j > 0 ? j - 1 : j, c2 = j < W - 1 ? j + 1 : j;
+  float mx = fmaxf(fmaxf(al[r0 + c0], al[r0 + j]), al[r0 + c2]);
+  mx = fmaxf(mx, fmaxf(fmaxf(al[r1 + c0], al[r1 + j]), al[r1 + c2]));
+  mx = fmaxf(mx, fmaxf(fmaxf(al[r2 + c0], al[r2 + j]), al[r2 + c2]));
+  return mx;
+}
+
+// (1/C) sum_c |(W_M x(p) + b_M)_c| of one cell, the channels added in index order.  GROUPS: also the
+// channel-group means g[0..2] of the same |m_c| (channels 0..2, 3, 4..C-1; an empty group is 0).  The
+// one statement of this sum: gnca_attn_sfield and gnca_diag_field produce the same bits.
+template <int CP, bool GROUPS>
+__device__ inline float attn_cell_absmean(const float* xb, int p, int HW, int C, const float* wms,
+                                          const float* bms, float* g) {
+  float xv[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) xv[c] = c < C ? xb[(size_t)c * HW + p] : 0.f;
+  float s = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f;
+  for (int co = 0; co < C; ++co) {
+    float m = bms[co];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) m = fmaf(wms[co * CP + c], xv[c], m);
+    const float am = fabsf(m);
+    s += am;
+    if (GROUPS) {   // (selects, not branches: the loop stays one loop; + 0 is exact)
+      g0 += co < 3 ? am : 0.f;
+      g1 += co == 3 ? am : 0.f;
+      g2 += co > 3 ? am : 0.f;
+    }
+  }
+  s /= (float)C;
+  if (GROUPS) {
+    g[0] = g0 / 3.f;
+    g[1] = g1;
+    g[2] = C > 4 ? g2 / (float)(C - 4) : 0.f;
+  }
+  return s;
+}
+
+// one tap of the gather, raw + w * s as ONE fused multiply-add: what the compiler contracts the plain
+// expression into, stated so that gnca_attn_gather and gnca_diag_gather cannot come to differ
+__device__ inline float attn_tap(float raw, float w, float s) { return fmaf(w, s, raw); }
+
+// S(p) for every cell: CP = the channel count rounded up to 16 (registers hold the cell's channels)
+template <int CP>
+__global__ __launch_bounds__(kThreads) void gnca_attn_sfield(const AttnArgs a) {
+  __shared__ float wms[CP * CP];
+  __shared__ float bms[CP];
+  const int C = a.C, H = a.H, W = a.W, HW = H * W;
+  attn_load_wm<CP>(a, wms, bms);
   const int p = blockIdx.x * kThreads + threadIdx.x;
   if (p >= HW) return;
   const int i = p / W, j = p - i * W;
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     const float* xb = a.x + (size_t)b * C * HW;
     bool send = true;
-    if (a.a2a) {
-      // 3x3 max-pool of alpha with -inf padding: the window clamped at the image edge repeats an
-      // in-window value (the same max)
-      const float* al = xb + (size_t)3 * HW;
-      const int r0 = (i > 0 ? i - 1 : i) * W, r1 = i * W, r2 = (i < H - 1 ? i + 1 : i) * W;
-      const int c0 = j > 0 ? j - 1 : j, c2 = j < W - 1 ? j + 1 : j;
-      float mx = fmaxf(fmaxf(al[r0 + c0], al[r0 + j]), al[r0 + c2]);
-      mx = fmaxf(mx, fmaxf(fmaxf(al[r1 + c0], al[r1 + j]), al[r1 + c2]));
-      mx = fmaxf(mx, fmaxf(fmaxf(al[r2 + c0], al[r2 + j]), al[r2 + c2]));
-      send = mx > a.gthr;
-    }
+    if (a.a2a) send = attn_pooled_alpha(xb + (size_t)3 * HW, i, j, H, W) > a.gthr;
     float s = 0.f;
-    if (send) {   // (a dead sender's S is 0 whatever its message)
-      float xv[CP];
-#pragma unroll
-      for (int c = 0; c < CP; ++c) xv[c] = c < C ? xb[(size_t)c * HW + p] : 0.f;
-      for (int co = 0; co < C; ++co) {
-        float m = bms[co];
-#pragma unroll
-        for (int c = 0; c < CP; ++c) m = fmaf(wms[co * CP + c], xv[c], m);
-        s += fabsf(m);
-      }
-      s /= (float)C;
-    }
+    // (a dead sender's S is 0 whatever its message)
+    if (send) s = attn_cell_absmean<CP, false>(xb, p, HW, C, wms, bms, nullptr);
     a.S[(size_t)b * HW + p] = s;
   }
 }
@@ -2976,14 +3009,14 @@ __global__ __launch_bounds__(kThreads) void gnca_attn_gather(const AttnArgs a) {
       for (int o = 0; o < k; ++o) {
         const int ii = i - a.oy[o];
         const float s = (ii >= 0 && ii < H) ? Sb[ii * W + j] : 0.f;
-        raw += wb[o] * s;
+        raw = attn_tap(raw, wb[o], s);
       }
     } else {
       for (int o = 0; o < k; ++o) {
         int ii = i - a.oy[o], jj = j - a.ox[o];
         ii = ii < 0 ? ii + H : ii;
         jj = jj < 0 ? jj + W : jj;
-        raw += a.uniform_w * Sb[ii * W + jj];
+        raw = attn_tap(raw, a.uniform_w, Sb[ii * W + jj]);
       }
     }
     if (ok) a.attn[(size_t)b * HW + p] = raw;
@@ -3013,6 +3046,41 @@ __global__ __launch_bounds__(kThreads) void gnca_attn_finish(float* attn, const 
   }
 }
 
+// the zero-padded shift's per-sample offset weights into the workspace: the step's own K0
+static int attn_launch_k0(const gnca_step_desc* d, const gnca_weights* w, const AttnLayout& L, const float* x,
+                          char* wsb, hipStream_t st) {
+  Plan P;   // launch_k0 reads only these Plan fields
+  memset(&P, 0, sizeof(P));
+  P.k = L.k;
+  P.off_offw = L.off_offw;
+  P.off_rs = L.off_rs;
+  return launch_k0(d, w, P, x, wsb, st);
+}
+
+// the arguments gnca_attn_sfield / gnca_attn_gather (and their diagnostic twins) share, for a layout
+// that is on (k > 0); the weights may be null when no kernel reads them
+static void attn_fill_args(const gnca_step_desc* d, const gnca_weights* w, const AttnLayout& L, const float* x,
+                           char* wsb, float* attn, AttnArgs* pa) {
+  AttnArgs& a = *pa;
+  memset(&a, 0, sizeof(a));
+  a.x = x;
+  if (w) { a.wm = w->wm; a.bm = w->bm; }
+  a.offw = L.zp ? reinterpret_cast<const float*>(wsb + L.off_offw) : nullptr;
+  a.S = L.on ? reinterpret_cast<float*>(wsb + L.off_S) : nullptr;
+  a.attn = attn;
+  a.mm = L.on ? reinterpret_cast<float*>(wsb + L.off_mm) : nullptr;
+  a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W; a.k = L.k; a.nblk = L.nblk;
+  a.zp = L.zp ? 1 : 0;
+  a.a2a = (d->flags & GNCA_ALIVE_TO_ALIVE) ? 1 : 0;
+  a.gthr = d->graph_alpha_thr;
+  a.uniform_w = L.k > 0 ? (float)(1.0 / (double)L.k) : 0.f;
+  for (int o = 0; o < L.k; ++o) {
+    const int dy = d->offsets[2 * o], dx = d->offsets[2 * o + 1];
+    a.oy[o] = (int16_t)(L.zp ? dy : ((dy % d->H) + d->H) % d->H);
+    a.ox[o] = (int16_t)(L.zp ? 0 : ((dx % d->W) + d->W) % d->W);
+  }
+}
+
 static int attention_impl(const gnca_step_desc* d, const gnca_weights* w, const float* x, float* attn, void* ws,
                           size_t ws_bytes, hipStream_t st) {
   AttnLayout L;
@@ -3026,31 +3094,9 @@ static int attention_impl(const gnca_step_desc* d, const gnca_weights* w, const 
   if (!ws || ws_bytes < L.bytes) return GNCA_ERR_WORKSPACE;
   char* wsb = reinterpret_cast<char*>(ws);
   int rc;
-  if (L.zp) {   // the step's own K0: launch_k0 reads only these Plan fields
-    Plan P;
-    memset(&P, 0, sizeof(P));
-    P.k = L.k;
-    P.off_offw = L.off_offw;
-    P.off_rs = L.off_rs;
-    if ((rc = launch_k0(d, w, P, x, wsb, st)) != GNCA_OK) return rc;
-  }
+  if (L.zp && (rc = attn_launch_k0(d, w, L, x, wsb, st)) != GNCA_OK) return rc;
   AttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.wm = w->wm; a.bm = w->bm;
-  a.offw = L.zp ? reinterpret_cast<const float*>(wsb + L.off_offw) : nullptr;
-  a.S = reinterpret_cast<float*>(wsb + L.off_S);
-  a.attn = attn;
-  a.mm = reinterpret_cast<float*>(wsb + L.off_mm);
-  a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W; a.k = L.k; a.nblk = L.nblk;
-  a.zp = L.zp ? 1 : 0;
-  a.a2a = (d->flags & GNCA_ALIVE_TO_ALIVE) ? 1 : 0;
-  a.gthr = d->graph_alpha_thr;
-  a.uniform_w = (float)(1.0 / (double)L.k);
-  for (int o = 0; o < L.k; ++o) {
-    const int dy = d->offsets[2 * o], dx = d->offsets[2 * o + 1];
-    a.oy[o] = (int16_t)(L.zp ? dy : ((dy % d->H) + d->H) % d->H);
-    a.ox[o] = (int16_t)(L.zp ? 0 : ((dx % d->W) + d->W) % d->W);
-  }
+  attn_fill_args(d, w, L, x, wsb, attn, &a);
   // torus: the wrapped offsets must fit int16 (canvases up to 32767 rows / columns)
   if (!L.zp && (d->H > 32767 || d->W > 32767)) return GNCA_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)L.nblk, (unsigned)std::min(d->B, 65535));
@@ -3063,6 +3109,194 @@ static int attention_impl(const gnca_step_desc* d, const gnca_weights* w, const 
   if ((rc = check_launch()) != GNCA_OK) return rc;
   const dim3 gridn((unsigned)std::min(L.nblk, 64), grid.y);
   hipLaunchKernelGGL(gnca_attn_finish, gridn, dim3(kThreads), 0, st, attn, a.mm, d->B, L.nblk, (int)HW);
+  return check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Graph diagnostics: the same factorisation, decomposed.  The field kernel writes, beside
+// S, the three masked channel-group planes src * G_g and the src byte (and the unmasked G_g and the
+// receiver mask straight to the outputs); the gather takes the k taps of those planes in offset order
+// and writes the un-normalised map, the group maps, the sender union and every single tap.
+//   gnca_diag_field   S, src * G_g [3], src -> workspace; magnitude, receiver -> outputs
+//   gnca_diag_gather  raw, groups, sender_union, per_offset, weights; (min, max) of raw per workgroup
+//   gnca_attn_finish  attention = raw normalised (the attention op's own kernel)
+// ---------------------------------------------------------------------------------------------
+struct DiagArgs {
+  AttnArgs a;          // a.attn: the attention output (receives raw, then normalised in place) or null
+  float* GM;           // workspace [B, 3, H, W]: src * G_g
+  uint8_t* src;        // workspace [B, H, W]
+  float* magnitude;    // outputs, each may be null
+  float* receiver;
+  float* raw;
+  float* groups;
+  float* per_offset;
+  float* sender_union;
+  float* weights;
+  int msg;             // 0: graph off (no message projection: magnitude is zero)
+  int planes;          // the field kernel also writes S, GM and src (k > 0)
+};
+
+struct DiagLayout {
+  AttnLayout A;
+  size_t off_G, off_src, bytes;
+};
+
+static bool diag_layout(const gnca_step_desc* d, DiagLayout* L) {
+  if (!attn_layout(d, &L->A)) return false;
+  const size_t HW = (size_t)d->H * d->W;
+  size_t o = L->A.bytes;
+  auto carve = [&o](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  L->off_G = carve(L->A.on ? (size_t)d->B * 3 * HW * sizeof(float) : 0);
+  L->off_src = carve(L->A.on ? (size_t)d->B * HW : 0);
+  L->bytes = o;
+  return true;
+}
+
+template <int CP>
+__global__ __launch_bounds__(kThreads) void gnca_diag_field(const DiagArgs d) {
+  __shared__ float wms[CP * CP];
+  __shared__ float bms[CP];
+  const AttnArgs& a = d.a;
+  const int C = a.C, H = a.H, W = a.W, HW = H * W;
+  if (d.msg) attn_load_wm<CP>(a, wms, bms);   // (uniform over the grid)
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= HW) return;
+  const int i = p / W, j = p - i * W;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    const float* xb = a.x + (size_t)b * C * HW;
+    const bool alive = attn_pooled_alpha(xb + (size_t)3 * HW, i, j, H, W) > a.gthr;
+    const bool send = a.a2a ? alive : true;
+    float g[3] = {0.f, 0.f, 0.f};
+    float s = 0.f;
+    if (d.msg) s = attn_cell_absmean<CP, true>(xb, p, HW, C, wms, bms, g);
+    const size_t bp = (size_t)b * HW + p;
+    if (d.receiver) d.receiver[bp] = alive ? 1.f : 0.f;
+#pragma unroll
+    for (int gi = 0; gi < 3; ++gi) {
+      const size_t at = ((size_t)b * 3 + gi) * HW + p;
+      if (d.magnitude) d.magnitude[at] = g[gi];
+      if (d.planes) d.GM[at] = send ? g[gi] : 0.f;
+    }
+    if (d.planes) {
+      a.S[bp] = send ? s : 0.f;
+      d.src[bp] = send ? 1 : 0;
+    }
+  }
+}
+
+// the k taps of S, src * G_g and src per cell, o = 0 .. k-1 in order (gnca_attn_gather's shifts)
+__global__ __launch_bounds__(kThreads) void gnca_diag_gather(const DiagArgs d) {
+  __shared__ float red[2 * (kThreads / 64)];
+  const AttnArgs& a = d.a;
+  const int H = a.H, W = a.W, HW = H * W, k = a.k;
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  const bool ok = p < HW;
+  const int pc = ok ? p : HW - 1;
+  const int i = pc / W, j = pc - i * W;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    const float* Sb = a.S + (size_t)b * HW;
+    const float* Gb = d.GM + (size_t)b * 3 * HW;
+    const uint8_t* srcb = d.src + (size_t)b * HW;
+    const float* wb = a.zp ? a.offw + (size_t)b * k : nullptr;
+    float* pob = d.per_offset ? d.per_offset + (size_t)b * k * HW + pc : nullptr;
+    float raw = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f;
+    int un = 0;
+    for (int o = 0; o < k; ++o) {
+      int ii = i - a.oy[o], jj = j;
+      bool in = true;
+      float wo;
+      if (a.zp) {
+        wo = wb[o];
+        in = ii >= 0 && ii < H;
+      } else {
+        wo = a.uniform_w;
+        jj = j - a.ox[o];
+        ii = ii < 0 ? ii + H : ii;
+        jj = jj < 0 ? jj + W : jj;
+      }
+      const int at = in ? ii * W + jj : 0;
+      const float s = in ? Sb[at] : 0.f;
+      raw = attn_tap(raw, wo, s);
+      q0 = attn_tap(q0, wo, in ? Gb[at] : 0.f);
+      q1 = attn_tap(q1, wo, in ? Gb[HW + at] : 0.f);
+      q2 = attn_tap(q2, wo, in ? Gb[2 * HW + at] : 0.f);
+      un |= in ? (int)srcb[at] : 0;
+      if (pob && ok) pob[(size_t)o * HW] = wo * s;
+    }
+    if (ok) {
+      const size_t bp = (size_t)b * HW + p;
+      if (a.attn) a.attn[bp] = raw;
+      if (d.raw) d.raw[bp] = raw;
+      if (d.groups) {
+        d.groups[((size_t)b * 3 + 0) * HW + p] = q0;
+        d.groups[((size_t)b * 3 + 1) * HW + p] = q1;
+        d.groups[((size_t)b * 3 + 2) * HW + p] = q2;
+      }
+      // (without alive_to_alive the reference draws no sender mask: zeros)
+      if (d.sender_union) d.sender_union[bp] = (a.a2a && un) ? 1.f : 0.f;
+    }
+    if (d.weights && blockIdx.x == 0)
+      for (int o = threadIdx.x; o < k; o += kThreads) d.weights[(size_t)b * k + o] = a.zp ? wb[o] : a.uniform_w;
+    attn_block_minmax(ok ? raw : INFINITY, ok ? raw : -INFINITY, red,
+                      a.mm + ((size_t)b * a.nblk + blockIdx.x) * 2);
+  }
+}
+
+static int diag_zero(float* p, size_t n, hipStream_t st) {
+  if (!p || n == 0) return GNCA_OK;
+  return hipMemsetAsync(p, 0, n * sizeof(float), st) == hipSuccess ? GNCA_OK : GNCA_ERR_HIP;
+}
+
+static int diag_impl(const gnca_step_desc* d, const gnca_weights* w, const float* x, const gnca_graph_diag_out* out,
+                     void* ws, size_t ws_bytes, hipStream_t st) {
+  DiagLayout D;
+  if (!diag_layout(d, &D)) return (d && d->C > 32) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  const AttnLayout& L = D.A;
+  if (!x || !out) return GNCA_ERR_INVALID;
+  const bool graph = (d->flags & GNCA_GRAPH) != 0;
+  if (graph && (!w || !w->wm || !w->bm)) return GNCA_ERR_INVALID;
+  if (L.zp && (!w->wq || !w->bq || !w->wk || !w->bk || !w->scaling)) return GNCA_ERR_INVALID;
+  if (L.on && (!ws || ws_bytes < D.bytes)) return GNCA_ERR_WORKSPACE;
+  // torus: the wrapped offsets must fit int16 (canvases up to 32767 rows / columns)
+  if (L.on && !L.zp && (d->H > 32767 || d->W > 32767)) return GNCA_ERR_UNSUPPORTED;
+  const bool gathered = out->groups || out->per_offset || out->raw || out->attention || out->sender_union ||
+                        out->weights;
+  const bool planes = L.on && gathered;
+  if (!gathered && !out->magnitude && !out->receiver) return GNCA_OK;   // nothing is requested
+  const size_t HW = (size_t)d->H * d->W, BHW = (size_t)d->B * HW;
+  char* wsb = reinterpret_cast<char*>(ws);
+  int rc;
+  if (planes && L.zp && (rc = attn_launch_k0(d, w, L, x, wsb, st)) != GNCA_OK) return rc;
+  DiagArgs g;
+  memset(&g, 0, sizeof(g));
+  attn_fill_args(d, graph ? w : nullptr, L, x, wsb, planes ? out->attention : nullptr, &g.a);
+  g.GM = planes ? reinterpret_cast<float*>(wsb + D.off_G) : nullptr;
+  g.src = planes ? reinterpret_cast<uint8_t*>(wsb + D.off_src) : nullptr;
+  g.magnitude = out->magnitude; g.receiver = out->receiver;
+  g.raw = out->raw; g.groups = out->groups; g.per_offset = out->per_offset;
+  g.sender_union = out->sender_union; g.weights = out->weights;
+  g.msg = graph ? 1 : 0;
+  g.planes = planes ? 1 : 0;
+  const dim3 grid((unsigned)L.nblk, (unsigned)std::min(d->B, 65535));
+  if (planes || out->magnitude || out->receiver) {
+    if (d->C <= 16)
+      hipLaunchKernelGGL(gnca_diag_field<16>, grid, dim3(kThreads), 0, st, g);
+    else
+      hipLaunchKernelGGL(gnca_diag_field<32>, grid, dim3(kThreads), 0, st, g);
+    if ((rc = check_launch()) != GNCA_OK) return rc;
+  }
+  if (!L.on) {   // graph off or no offsets: zeros; per_offset and weights have no elements
+    if ((rc = diag_zero(out->groups, 3 * BHW, st)) != GNCA_OK) return rc;
+    if ((rc = diag_zero(out->raw, BHW, st)) != GNCA_OK) return rc;
+    if ((rc = diag_zero(out->attention, BHW, st)) != GNCA_OK) return rc;
+    return diag_zero(out->sender_union, BHW, st);
+  }
+  if (!planes) return GNCA_OK;
+  hipLaunchKernelGGL(gnca_diag_gather, grid, dim3(kThreads), 0, st, g);
+  if ((rc = check_launch()) != GNCA_OK) return rc;
+  if (!out->attention) return GNCA_OK;
+  const dim3 gridn((unsigned)std::min(L.nblk, 64), grid.y);
+  hipLaunchKernelGGL(gnca_attn_finish, gridn, dim3(kThreads), 0, st, out->attention, g.a.mm, d->B, L.nblk, (int)HW);
   return check_launch();
 }
 
@@ -3091,13 +3325,14 @@ static int frame_copy(const float* src, float* dst, int B, int fc, int C, size_t
   return check_launch();
 }
 
-// [state A | state B | scratch | rollout workspace | attention workspace | metrics workspace]
+// [state A | state B | scratch | rollout workspace | attention workspace | metrics workspace |
+//  diagnostics workspace]
 struct TraceLayout {
-  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, off_met, met_ws, bytes;
+  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, off_met, met_ws, off_diag, diag_ws, bytes;
 };
 
 static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, const gnca_trace_metrics* m,
-                         TraceLayout* L) {
+                         TraceLayout* L, bool diag = false) {
   if (!d || !a || a->steps < 0 || a->num_records < 0 || a->flags != 0) return false;
   if (a->num_records > 0 && !a->record) return false;
   for (int r = 0; r < a->num_records; ++r) {
@@ -3131,19 +3366,42 @@ static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, cons
   L->off_attn = L->off_ws + L->ws;
   L->off_met = L->off_attn + L->attn_ws;
   L->met_ws = m ? (gnca_image_metrics_workspace_bytes(d->B, d->H, d->W) + 255) & ~(size_t)255 : 0;
-  L->bytes = L->off_met + L->met_ws;
+  L->off_diag = L->off_met + L->met_ws;
+  L->diag_ws = 0;
+  if (diag) {
+    DiagLayout D;
+    if (!diag_layout(&dt, &D)) return false;
+    L->diag_ws = D.bytes;
+  }
+  L->bytes = L->off_diag + L->diag_ws;
   return true;
 }
 
-// gnca_rollout_trace_f32 (m == nullptr) / gnca_rollout_trace_metrics_f32
+// record r's slice of the [R, ...]-leading diagnostic outputs
+static gnca_graph_diag_out diag_record(const gnca_graph_diag_out& o, size_t r, size_t B, size_t k, size_t HW) {
+  auto at = [r](float* p, size_t per) { return p ? p + r * per : nullptr; };
+  gnca_graph_diag_out q;
+  q.magnitude = at(o.magnitude, B * 3 * HW);
+  q.groups = at(o.groups, B * 3 * HW);
+  q.per_offset = at(o.per_offset, B * k * HW);
+  q.raw = at(o.raw, B * HW);
+  q.attention = at(o.attention, B * HW);
+  q.sender_union = at(o.sender_union, B * HW);
+  q.receiver = at(o.receiver, B * HW);
+  q.weights = at(o.weights, B * k);
+  return q;
+}
+
+// gnca_rollout_trace_f32 (m == nullptr) / gnca_rollout_trace_metrics_f32 / gnca_rollout_trace_diag (diag set)
 static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
                       const gnca_trace_metrics* m, const float* x, float* x_final, void* ws, size_t ws_bytes,
-                      void* stream) {
+                      void* stream, const gnca_graph_diag_out* diag = nullptr) {
   if (!desc || !w || !args || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
   TraceLayout L;
-  if (!trace_layout(desc, args, m, &L)) return GNCA_ERR_INVALID;
+  if (!trace_layout(desc, args, m, &L, diag != nullptr))
+    return (diag && desc->C > 32) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
   const int T = args->steps, R = args->num_records, fc = args->frame_channels;
-  if (R > 0 && !args->frames && !m) return GNCA_ERR_INVALID;
+  if (R > 0 && !args->frames && !m && !diag) return GNCA_ERR_INVALID;
   // (target and out both NULL: nothing is measured, a trace that may go without frames)
   if (m && (m->target_bstride < 0 || (m->target == nullptr) != (m->out == nullptr))) return GNCA_ERR_INVALID;
   const bool measure = m && m->out;
@@ -3160,7 +3418,8 @@ static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const g
   const size_t HW = (size_t)desc->H * desc->W;
   gnca_step_desc dt = *desc;
   dt.flags &= ~GNCA_ATTENTION;
-  const bool maps = args->attn != nullptr;
+  // maps: something is computed from the input state of every recorded step
+  const bool maps = args->attn != nullptr || diag != nullptr;
   if (T == 0)
     return hipMemcpyAsync(x_final, x, (size_t)desc->B * desc->C * HW * sizeof(float), hipMemcpyDeviceToDevice,
                           st) == hipSuccess ? GNCA_OK : GNCA_ERR_HIP;
@@ -3174,9 +3433,13 @@ static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const g
     int rc;
     if (maps && r < R && args->record[r] == t0 + 1) {   // the map of step t0 + 1, from its input state
       if (offs) memcpy(dt.offsets, args->offsets + (size_t)t0 * 2 * k, 2 * k);
-      if ((rc = attention_impl(&dt, w, cur, args->attn + (size_t)r * desc->B * HW, wsb + L.off_attn, L.attn_ws,
-                               st)) != GNCA_OK)
+      if (args->attn && (rc = attention_impl(&dt, w, cur, args->attn + (size_t)r * desc->B * HW, wsb + L.off_attn,
+                                             L.attn_ws, st)) != GNCA_OK)
         return rc;
+      if (diag) {
+        const gnca_graph_diag_out q = diag_record(*diag, (size_t)r, (size_t)desc->B, offs ? (size_t)k : 0, HW);
+        if ((rc = diag_impl(&dt, w, cur, &q, wsb + L.off_diag, L.diag_ws, st)) != GNCA_OK) return rc;
+      }
     }
     int t1 = T;
     if (r < R) t1 = (maps && args->record[r] - 1 > t0) ? args->record[r] - 1 : args->record[r];
@@ -3241,6 +3504,31 @@ int gnca_rollout_trace_metrics_f32(const gnca_step_desc* desc, const gnca_weight
                                    size_t ws_bytes, void* stream) {
   if (!m) return GNCA_ERR_INVALID;
   return trace_impl(desc, w, args, m, x, x_final, ws, ws_bytes, stream);
+}
+
+size_t gnca_graph_diag_workspace_bytes(const gnca_step_desc* desc) {
+  DiagLayout D;
+  return diag_layout(desc, &D) ? std::max<size_t>(D.bytes, 256) : 0;
+}
+
+int gnca_graph_diag(const gnca_step_desc* desc, const gnca_weights* w, const float* x,
+                    const gnca_graph_diag_out* out, void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StreamDeviceGuard dg(st);
+  return diag_impl(desc, w, x, out, ws, ws_bytes, st);
+}
+
+size_t gnca_rollout_trace_diag_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                               const gnca_trace_metrics* m) {
+  TraceLayout L;
+  return trace_layout(desc, args, m, &L, true) ? L.bytes : 0;
+}
+
+int gnca_rollout_trace_diag(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                            const gnca_trace_metrics* m, const gnca_graph_diag_out* diag, const float* x,
+                            float* x_final, void* ws, size_t ws_bytes, void* stream) {
+  if (!diag) return GNCA_ERR_INVALID;
+  return trace_impl(desc, w, args, m, x, x_final, ws, ws_bytes, stream, diag);
 }
 
 }  // extern "C"

@@ -360,32 +360,43 @@ class TraceResult:
     each recorded step), ``steps`` (the R recorded step indices, counted from 1 within this call) and
     ``attention`` [R,B,H,W] (the map of each recorded step) or None; ``metrics``, an ``ImageMetrics``
     of shape [R,B] (the state after each recorded step against ``target``) or None.  ``frames`` is
-    None for a trace with ``frames=False``.  All detached."""
+    None for a trace with ``frames=False``.  ``diagnostics``: a ``GraphDiagnostics`` whose fields lead
+    with the R axis (each recorded step's input state with that step's offsets) or None.  All detached."""
 
-    __slots__ = ("x_final", "frames", "steps", "attention", "metrics")
+    __slots__ = ("x_final", "frames", "steps", "attention", "metrics", "diagnostics")
 
-    def __init__(self, x_final, frames, steps, attention, metrics=None):
+    def __init__(self, x_final, frames, steps, attention, metrics=None, diagnostics=None):
         self.x_final, self.frames, self.steps, self.attention = x_final, frames, steps, attention
         self.metrics = metrics
+        self.diagnostics = diagnostics
 
     def __repr__(self):
         shape = lambda t: None if t is None else tuple(t.shape)
         return (f"TraceResult(steps={self.steps}, frames={shape(self.frames)}, "
                 f"attention={shape(self.attention)}, "
-                f"metrics={None if self.metrics is None else shape(self.metrics.stacked)})")
+                f"metrics={None if self.metrics is None else shape(self.metrics.stacked)}"
+                + ("" if self.diagnostics is None else ", diagnostics") + ")")
 
 
 def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, every=1, record=None,
               channels=4, return_attention=False, fire_rate=1.0, message_gain=None, seed=None, sample_base=0,
-              first_step=0, offsets=None, target=None, frames=True) -> TraceResult:
+              first_step=0, offsets=None, target=None, frames=True, diagnostics=False,
+              per_offset=False) -> TraceResult:
     """The shared body of ``NeuralCA.trace`` / ``NeuralCAGraph.trace``: a no-grad rollout that records
-    frames (and attention maps, and image metrics against ``target``) in one native call."""
+    frames (and attention maps, image metrics against ``target`` and graph diagnostics) in one native
+    call."""
     if x.dim() != 4:
         raise ValueError(f"state must be [B,C,H,W], got {tuple(x.shape)}")
     B, C, H, W = x.shape
     _check_norm(model)
     if not isinstance(frames, bool):
         raise ValueError(f"frames must be a bool, got {frames!r}")
+    if not isinstance(diagnostics, bool) or not isinstance(per_offset, bool):
+        raise ValueError(f"diagnostics and per_offset must be bools, got {diagnostics!r}, {per_offset!r}")
+    if diagnostics and graph is None:
+        raise ValueError("diagnostics needs the graph term: this model has none")
+    if per_offset and not diagnostics:
+        raise ValueError("per_offset is part of the diagnostics: pass diagnostics=True")
     if target is not None:
         target = M.check_target(target, B, H, W)
     # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
@@ -398,8 +409,14 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
         sched = plan.schedule
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
         desc.rng_step = plan.first_step
-        met = None
-        if target is None and frames:
+        met = diag = None
+        if diagnostics:
+            tgt, tbs = (None, 0) if target is None else M.device_target(target, x.device)
+            out, frm, attn, met, diag = S.trace_diag(desc, w, x, steps, sched.offsets or [], plan.record,
+                                                     plan.channels, tgt, tbs, want_attention=plan.attention,
+                                                     want_frames=frames, per_offset=per_offset)
+            met = None if met is None else M.ImageMetrics(met)
+        elif target is None and frames:
             out, frm, attn = S.trace(desc, w, x, steps, sched.offsets or [], plan.record, plan.channels,
                                      want_attention=plan.attention)
         else:
@@ -409,4 +426,4 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
                                                   want_frames=frames)
             met = None if met is None else M.ImageMetrics(met)
         del keep
-    return TraceResult(out, frm, list(plan.record), attn, met)
+    return TraceResult(out, frm, list(plan.record), attn, met, diag)

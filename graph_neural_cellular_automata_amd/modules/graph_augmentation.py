@@ -114,3 +114,46 @@ class GraphAugmentation(nn.Module):
         attn = S.attention_map(desc, w, x)
         del keep
         return attn
+
+    @staticmethod
+    def _check_offsets(offsets):
+        """``offsets`` as a list of int (dy, dx) pairs; ``ValueError`` on anything else."""
+        try:
+            pairs = [tuple(o) for o in offsets]
+        except TypeError:
+            raise ValueError(f"offsets must be a sequence of (dy, dx) pairs, got {offsets!r}") from None
+        for o in pairs:
+            if len(o) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in o):
+                raise ValueError(f"offsets must hold (dy, dx) int pairs, got {o!r}")
+            if not all(-127 <= v <= 127 for v in o):
+                raise ValueError(f"offset {o} out of int8 range")
+        if len(pairs) > L.MAX_OFFSETS:
+            raise ValueError(f"at most {L.MAX_OFFSETS} offsets per step (got {len(pairs)})")
+        return pairs
+
+    @torch.no_grad()
+    def diagnostics(self, x: torch.Tensor, offsets=None, *, per_offset: bool = True) -> S.GraphDiagnostics:
+        """The decomposition of the attention map that the reference's evaluation scripts draw
+        (src/testing/test_graph_augmented_nca.py:77-158 and the per-group ``|M|`` maps of
+        src/testing/test_graph_augmented_regeneration.py:196-204), for any batch, on the device
+        (extension): a ``GraphDiagnostics`` with ``magnitude``, ``groups``, ``per_offset``, ``raw``,
+        ``attention`` (bitwise ``attention_map(x, offsets)``), ``sender_union``, ``receiver``,
+        ``weights`` and the ``offsets`` used.  ``offsets=None`` draws ``sample_offsets()`` (one
+        ``random.sample``), else a list of (dy, dx) pairs; ``per_offset=False`` skips the [B,k,H,W]
+        stack.  Bad arguments raise ``ValueError`` before anything is drawn.  No gradient."""
+        if not isinstance(per_offset, bool):
+            raise ValueError(f"per_offset must be a bool, got {per_offset!r}")
+        if x.dim() != 4 or x.shape[1] != self.n_channels or self.n_channels < 4:
+            raise ValueError(f"state must be [B,{self.n_channels},H,W] with at least 4 channels, got {tuple(x.shape)}")
+        chosen = None if offsets is None else self._check_offsets(offsets)
+        x = S.check_state(x.detach(), self.n_channels)
+        if chosen is None:
+            chosen = self.sample_offsets()
+        B, C, H, W = x.shape
+        desc = S.make_desc(B=B, C=C, H=H, W=W, hidden=1, d_model=self.d_model, offsets=chosen,
+                           flags=self.flags(False), update_gain=0.0, alpha_thr=self.alpha_thr,
+                           message_gain=1.0, fire_rate=1.0, fire_mode=L.FIRE_NONE)
+        w, keep = S.make_weights(self.weight_tensors())
+        diag = S.graph_diagnostics(desc, w, x, per_offset=per_offset)
+        del keep
+        return diag

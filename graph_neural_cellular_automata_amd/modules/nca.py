@@ -46,13 +46,15 @@ class NeuralCA(nn.Module):
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
               sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
-              frames: bool = True) -> TraceResult:
+              frames: bool = True, diagnostics: bool = False, per_offset: bool = False) -> TraceResult:
         """``steps`` CA steps in one native call that also records frames: see ``NeuralCAGraph.trace``
         (same arguments and result; always under ``no_grad``, detached tensors).  The classic model
-        has no graph term: ``return_attention=True``, a ``message_gain`` or ``offsets`` raise
-        ``ValueError``."""
+        has no graph term: ``return_attention=True``, ``diagnostics=True``, a ``message_gain`` or
+        ``offsets`` raise ``ValueError``."""
         if return_attention:
             raise ValueError("return_attention: NeuralCA has no graph term, so no attention map")
+        if diagnostics or per_offset:
+            raise ValueError("diagnostics: NeuralCA has no graph term, so no graph diagnostics")
         if message_gain is not None:
             raise ValueError("message_gain given for a model without the graph term")
         return run_trace(self, x, steps, None, False, every=every, record=record, channels=channels,

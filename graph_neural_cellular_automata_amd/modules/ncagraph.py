@@ -98,7 +98,7 @@ class NeuralCAGraph(nn.Module):
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
               sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
-              frames: bool = True) -> TraceResult:
+              frames: bool = True, diagnostics: bool = False, per_offset: bool = False) -> TraceResult:
         """``steps`` CA steps in one native call that also records (extension, not in the reference):
         the per-step Python loop of the regeneration diagnostic and the video generators, on the
         rollout pipeline.  Always runs under ``no_grad`` and returns detached tensors, whatever the
@@ -124,9 +124,15 @@ class NeuralCAGraph(nn.Module):
         ``metrics`` is an ``ImageMetrics`` (mse, pixel_perfect, psnr, ssim; ``metrics.py``) of shape
         [R,B], the state after each recorded step against the target, bitwise
         ``image_metrics(frames, target)``.  ``frames=False`` allocates and records no frames
-        (``result.frames`` is None): a regeneration curve is then [R,B,4] floats and nothing else."""
+        (``result.frames`` is None): a regeneration curve is then [R,B,4] floats and nothing else.
+
+        ``diagnostics=True`` also records, for every recorded step, ``self.graph.diagnostics`` of that
+        step's input state with that step's offsets (the convention of ``attention``): the result's
+        ``diagnostics`` is a ``GraphDiagnostics`` whose fields lead with the R axis, bitwise the
+        standalone call's; ``per_offset=True`` includes the [R,B,k,H,W] stack.  The other results are
+        bitwise those of the trace without it."""
         return run_trace(self, x, steps, self.graph, self.hidden_only, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
                          message_gain=self.message_gain if message_gain is None else message_gain, seed=seed,
                          sample_base=sample_base, first_step=first_step, offsets=offsets, target=target,
-                         frames=frames)
+                         frames=frames, diagnostics=diagnostics, per_offset=per_offset)

@@ -546,7 +546,27 @@ def trace_metrics(desc, weights, x, steps: int, offsets_per_step: list, record: 
     of premultiplied RGBA with sample stride ``target_bstride``, 0 = broadcast; None: nothing is
     measured).  Returns ``(x_final, frames or None, attention or None, metrics [R,B,4] or None)``;
     without ``want_frames`` no frame buffer is allocated."""
+    return _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
+                           want_attention, want_frames, None)[:4]
+
+
+def trace_diag(desc, weights, x, steps: int, offsets_per_step: list, record: list, channels: int,
+               target=None, target_bstride: int = 0, want_attention: bool = False, want_frames: bool = True,
+               per_offset: bool = False):
+    """``trace_metrics`` that also records the diagnostics of every recorded step
+    (gnca_rollout_trace_diag), computed from that step's input state with that step's offsets.
+    Returns ``(x_final, frames or None, attention or None, metrics [R,B,4] or None, GraphDiagnostics
+    with [R,...]-leading fields)``."""
+    return _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
+                           want_attention, want_frames, bool(per_offset))
+
+
+def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
+                    want_attention, want_frames, diag_taps):
+    """The shared body of ``trace_metrics`` (``diag_taps`` None) and ``trace_diag`` (``diag_taps``: whether
+    the per-offset stack is recorded too)."""
     lib = L.load()
+    fn = _diag_entry("gnca_rollout_trace_diag") if diag_taps is not None else None
     k = desc.num_offsets
     flat = [v for offs in offsets_per_step for o in offs for v in o]
     if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
@@ -571,16 +591,103 @@ def trace_metrics(desc, weights, x, steps: int, offsets_per_step: list, record: 
         # (R = 0: a placeholder element keeps both pointers set; nothing is written)
         keep_out = met if R else torch.empty(4, dtype=torch.float32, device=x.device)
         m.target, m.target_bstride, m.out = target.data_ptr(), int(target_bstride), keep_out.data_ptr()
-    n = lib.gnca_rollout_trace_metrics_workspace_bytes(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
+    size = lib.gnca_rollout_trace_metrics_workspace_bytes if fn is None else lib.gnca_rollout_trace_diag_workspace_bytes
+    n = size(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
     if n == 0:
         raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
                           f"hidden={desc.hidden}")
     ws = torch.empty(n, dtype=torch.uint8, device=x.device)
-    rc = lib.gnca_rollout_trace_metrics_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a),
-                                            ctypes.byref(m), x.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), stream_ptr(x.device))
-    L.check(rc, "gnca_rollout_trace_metrics_f32")
-    return out, frames, attn, met
+    if fn is None:
+        rc = lib.gnca_rollout_trace_metrics_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a),
+                                                ctypes.byref(m), x.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                ws.numel(), stream_ptr(x.device))
+        L.check(rc, "gnca_rollout_trace_metrics_f32")
+        return out, frames, attn, met, None
+    t, o = _diag_buffers(desc, x.device, diag_taps, lead=(R,))
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), ctypes.byref(m), ctypes.byref(o),
+            x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+    L.check(rc, "gnca_rollout_trace_diag")
+    has = (desc.flags & L.GRAPH) and k > 0
+    offs = [[tuple(p) for p in offsets_per_step[r - 1]] if has else [] for r in record]
+    return out, frames, attn, met, GraphDiagnostics(offs, **t)
+
+
+class GraphDiagnostics:
+    """The decomposition of the attention map (``GraphAugmentation.diagnostics``, ``trace(diagnostics=True)``;
+    include/gnca.h, gnca_graph_diag_out).  With ``m = msg_proj(x)``, ``src`` the sender mask (1 without
+    ``alive_to_alive``), ``w_o`` the step's offset weights and ``S = src * mean_c |m_c|``, per sample
+    (a trace adds a leading ``R`` axis to every field):
+
+    ``magnitude`` [B,3,H,W]   mean |m_c| over the channels 0..2 / 3 / 4.. (unmasked, unweighted)
+    ``groups`` [B,3,H,W]      sum_o w_o shift_o(src * magnitude)
+    ``per_offset`` [B,k,H,W]  w_o shift_o(S), in offset order (None when not requested)
+    ``raw`` [B,H,W]           sum_o w_o shift_o(S): the un-normalised map
+    ``attention`` [B,H,W]     raw min-max normalised per sample: ``attention_map``, bitwise
+    ``sender_union`` [B,H,W]  {0,1}: max_o shift_o(src) with ``alive_to_alive``, else zeros
+    ``receiver`` [B,H,W]      {0,1}: the alive mask of the state
+    ``weights`` [B,k]         w_o
+    ``offsets``               the (dy, dx) pairs (a trace: one list per recorded step)
+
+    All detached float32 device tensors."""
+
+    __slots__ = L.DIAG_FIELDS + ("offsets",)
+
+    def __init__(self, offsets=None, **fields):
+        for n in L.DIAG_FIELDS:
+            setattr(self, n, fields.get(n))
+        self.offsets = offsets
+
+    def __repr__(self):
+        shape = lambda t: None if t is None else tuple(t.shape)
+        return "GraphDiagnostics(" + ", ".join(f"{n}={shape(getattr(self, n))}" for n in L.DIAG_FIELDS) + ")"
+
+
+def _diag_entry(name: str):
+    fn = getattr(L.load(), name, None)
+    if fn is None:
+        raise L.GncaError(f"libgnca.so lacks {name}: rebuild it")
+    return fn
+
+
+def _diag_buffers(desc, device, per_offset: bool, lead: tuple = ()):
+    """The output tensors of one diagnostics call (``lead``: a trace's record axis) and their struct."""
+    B, H, W = desc.B, desc.H, desc.W
+    k = desc.num_offsets if (desc.flags & L.GRAPH) else 0
+    f32 = torch.float32
+    t = {
+        "magnitude": torch.empty(*lead, B, 3, H, W, dtype=f32, device=device),
+        "groups": torch.empty(*lead, B, 3, H, W, dtype=f32, device=device),
+        "per_offset": torch.empty(*lead, B, k, H, W, dtype=f32, device=device) if per_offset else None,
+        "raw": torch.empty(*lead, B, H, W, dtype=f32, device=device),
+        "attention": torch.empty(*lead, B, H, W, dtype=f32, device=device),
+        "sender_union": torch.empty(*lead, B, H, W, dtype=f32, device=device),
+        "receiver": torch.empty(*lead, B, H, W, dtype=f32, device=device),
+        "weights": torch.empty(*lead, B, k, dtype=f32, device=device),
+    }
+    o = L.GraphDiagOut()
+    for n, v in t.items():
+        # (an empty tensor's data_ptr is 0: nothing is written)
+        setattr(o, n, v.data_ptr() if (v is not None and v.numel()) else None)
+    return t, o
+
+
+def graph_diagnostics(desc, weights, x, per_offset: bool = True) -> GraphDiagnostics:
+    """The diagnostics of state ``x`` for ``desc``'s offsets (gnca_graph_diag): a side computation, no
+    step."""
+    fn = _diag_entry("gnca_graph_diag")
+    lib = L.load()
+    t, o = _diag_buffers(desc, x.device, per_offset)
+    n = lib.gnca_graph_diag_workspace_bytes(ctypes.byref(desc))
+    if n == 0:
+        raise L.GncaError(f"unsupported diagnostics shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"k={desc.num_offsets}")
+    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), ctypes.byref(o), ws.data_ptr(), ws.numel(),
+            stream_ptr(x.device))
+    L.check(rc, "gnca_graph_diag")
+    k = desc.num_offsets if (desc.flags & L.GRAPH) else 0
+    offs = [(int(desc.offsets[2 * i]), int(desc.offsets[2 * i + 1])) for i in range(k)]
+    return GraphDiagnostics(offs, **t)
 
 
 class RolloutCall:

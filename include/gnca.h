@@ -46,6 +46,9 @@
  *   gnca_pool_commit         the pool write-back with worst-k reset and random reseed,
  *                            src/training/train_graph_augmented_nca.py:377-391 and
  *                            src/training/train_intermediate_loss.py:269-296
+ *   gnca_graph_diag          debug_graph_from_state, src/testing/test_graph_augmented_nca.py:77-158,
+ *                            and the |M| group maps of
+ *                            src/testing/test_graph_augmented_regeneration.py:196-204
  */
 #ifndef GNCA_H
 #define GNCA_H
@@ -468,6 +471,59 @@ size_t gnca_rollout_trace_metrics_workspace_bytes(const gnca_step_desc* desc, co
 int gnca_rollout_trace_metrics_f32(const gnca_step_desc* desc, const gnca_weights* w,
                                    const gnca_trace_args* args, const gnca_trace_metrics* m, const float* x,
                                    float* x_final, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Graph diagnostics: the decomposition of the attention map that the evaluation scripts draw
+ * (src/testing/test_graph_augmented_nca.py:77-158, debug_graph_from_state, and the per-group message
+ * magnitudes of src/testing/test_graph_augmented_regeneration.py:196-204), for any batch.  Neither
+ * name carries the _f32 suffix.
+ * -------------------------------------------------------------------------------------------*/
+
+/*
+ * With m = W_M x + b_M, src = the sender mask (3x3 max-pool of alpha > graph_alpha_thr) under
+ * GNCA_ALIVE_TO_ALIVE and 1 otherwise, w_o[b] the step's offset weights (1/k on the torus, the
+ * per-sample softmax of gnca_step_f32's zero-padded shift), shift_o the step's shift (torus roll;
+ * zero-padded: rows only, dx ignored), the channel groups g0 = 0..2, g1 = 3, g2 = 4..C-1 (empty when
+ * C = 4: zeros), G_g(p) = mean_{c in g} |m_c(p)| and S(p) = src(p) mean_c |m_c(p)|:
+ * all DEVICE fp32, any pointer may be NULL and is then skipped.
+ */
+typedef struct gnca_graph_diag_out {
+  float* magnitude;     /* [B,3,H,W]  G_g: unmasked, unweighted                                  */
+  float* groups;        /* [B,3,H,W]  sum_o w_o shift_o(src G_g)                                 */
+  float* per_offset;    /* [B,k,H,W]  w_o shift_o(S), in offset order                            */
+  float* raw;           /* [B,H,W]    sum_o w_o shift_o(S): the un-normalised map                */
+  float* attention;     /* [B,H,W]    raw min-max normalised per sample: gnca_attention_f32's map, bitwise */
+  float* sender_union;  /* [B,H,W]    {0,1}: max_o shift_o(src) under GNCA_ALIVE_TO_ALIVE, else zeros */
+  float* receiver;      /* [B,H,W]    {0,1}: 3x3 max-pool of alpha > graph_alpha_thr             */
+  float* weights;       /* [B,k]      w_o[b]                                                     */
+} gnca_graph_diag_out;
+
+/* Bytes of device workspace gnca_graph_diag needs for `desc` (0 on an invalid desc).  Host-only. */
+size_t gnca_graph_diag_workspace_bytes(const gnca_step_desc* desc);
+
+/*
+ * The diagnostics of state x for desc's offsets, without the step.  Reads the desc fields and weights
+ * gnca_attention_f32 reads (C <= 32).  num_offsets == 0: every map is zero except magnitude and
+ * receiver (per_offset and weights are empty); graph off: magnitude is zero too and no weight is read.
+ * Every requested output is written completely.  Fixed-order sums, no atomics: bitwise reproducible,
+ * and a sample's results do not depend on B or on its position in the batch.  per_offset summed over
+ * o equals raw to rounding (raw accumulates with fused multiply-adds).
+ */
+int gnca_graph_diag(const gnca_step_desc* desc, const gnca_weights* w, const float* x,
+                    const gnca_graph_diag_out* out, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * gnca_rollout_trace_metrics_f32 that also records the diagnostics of every recorded step, computed
+ * from that step's input state with that step's offsets (the convention of args->attn): `diag` holds
+ * [R,...]-leading versions of the outputs above ([R,B,3,H,W], [R,B,k,H,W], [R,B,H,W], [R,B,k]), any
+ * of them NULL.  metrics may be NULL (gnca_rollout_trace_f32's form).  The rollout's launches and the
+ * other outputs are those of the call without `diag`, bitwise.
+ */
+size_t gnca_rollout_trace_diag_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                               const gnca_trace_metrics* metrics);
+int gnca_rollout_trace_diag(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                            const gnca_trace_metrics* metrics, const gnca_graph_diag_out* diag, const float* x,
+                            float* x_final, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Step-adjacent batch op: damage (src/utils/damage.py:15-138).  ONE damage kind for the whole
