@@ -177,8 +177,37 @@ def rollout_fold(desc: L.StepDesc, possible: bool = False) -> bool:
     return bool(arith.value & (16 if possible else 8))
 
 
+_MULTI_GPU = None
+
+
 def stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+    """The current stream of ``device`` as the C ABI's ``void* stream``.
+
+    The null stream (pointer 0) names no device: the library would launch on whichever device is
+    current.  So a tensor on a device that is not the current one, on that device's default stream,
+    is refused instead of launched on the wrong device."""
+    ptr = torch.cuda.current_stream(device).cuda_stream
+    if ptr == 0 and _MULTI_GPU is not False:
+        _refuse_foreign_default_stream(device)
+    return ptr
+
+
+def _refuse_foreign_default_stream(device) -> None:
+    global _MULTI_GPU
+    if _MULTI_GPU is None:
+        _MULTI_GPU = torch.cuda.device_count() > 1
+    if not _MULTI_GPU:
+        return
+    idx = device.index if isinstance(device, torch.device) else torch.device(device).index
+    if idx is None:      # "cuda" without an index is the current device
+        return
+    cur = torch.cuda.current_device()
+    if idx != cur:
+        raise ValueError(
+            f"the tensors are on cuda:{idx} but the current device is cuda:{cur}, and cuda:{idx}'s "
+            f"current stream is its default stream, which does not name a device: the kernels would "
+            f"launch on cuda:{cur}.  Enter `with torch.cuda.device({idx}):` around the call, or use a "
+            f"stream of cuda:{idx} (`with torch.cuda.stream(torch.cuda.Stream({idx})):`)")
 
 
 def _active_u8(active, B, device):
