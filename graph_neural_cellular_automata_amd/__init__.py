@@ -4,5 +4,7 @@ The HIP kernels live in csrc/ and are built into libgnca.so (C ABI: include/gnca
 ``modules`` subpackage mirrors the reference's nn.Module API on top of it.
 """
 from .modules import FixedSobelPerception, GraphAugmentation, NeuralCA, NeuralCAGraph
+from .render import CMAPS, colorize, render_rgb
 
-__all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph"]
+__all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph",
+           "render_rgb", "colorize", "CMAPS"]

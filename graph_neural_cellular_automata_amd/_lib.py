@@ -133,6 +133,24 @@ class PoolCommitDesc(ctypes.Structure):
                 ("n_reset", ctypes.c_int32)]
 
 
+RENDER_RGB, RENDER_RGBA = 0, 1
+RENDER_BAND_ROWS = 8   # source rows one workgroup of gnca_render_u8 renders (include/gnca.h)
+NORM_MAX, NORM_MINMAX = 0, 1
+
+
+class RenderDesc(ctypes.Structure):
+    """Mirror of gnca_render_desc (include/gnca.h): the stream travels in the descriptor."""
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("upscale", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("alpha_thr", ctypes.c_float), ("src_nstride", ctypes.c_int64),
+                ("stream", ctypes.c_void_p)]
+
+
+class ColorizeDesc(ctypes.Structure):
+    """Mirror of gnca_colorize_desc (include/gnca.h): the stream travels in the descriptor."""
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("norm", ctypes.c_int32),
+                ("stream", ctypes.c_void_p)]
+
+
 DMG_SQUARE, DMG_CIRCLE, DMG_STRIPE_H, DMG_STRIPE_V = 0, 1, 2, 3
 DMG_ALPHA_DROP, DMG_ALPHA_DROP_SOFT, DMG_SALT_PEPPER, DMG_GAUSSIAN, DMG_HIDDEN_NOISE = 4, 5, 6, 7, 8
 
@@ -150,7 +168,7 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
            "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit",
            "gnca_graph_diag_workspace_bytes", "gnca_graph_diag", "gnca_rollout_trace_diag_workspace_bytes",
-           "gnca_rollout_trace_diag")
+           "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -289,6 +307,11 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_trace_diag.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                     ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics), do,
                                                     vp, vp, vp, sz, vp]
+        if hasattr(lib, "gnca_render_u8"):   # (likewise)
+            lib.gnca_render_u8.restype = ctypes.c_int
+            lib.gnca_render_u8.argtypes = [ctypes.POINTER(RenderDesc), vp, vp]
+            lib.gnca_colorize_u8.restype = ctypes.c_int
+            lib.gnca_colorize_u8.argtypes = [ctypes.POINTER(ColorizeDesc), vp, vp, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -8,6 +8,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import metrics as M
+from .. import render as R
 from .. import step as S
 
 
@@ -361,30 +362,37 @@ class TraceResult:
     ``attention`` [R,B,H,W] (the map of each recorded step) or None; ``metrics``, an ``ImageMetrics``
     of shape [R,B] (the state after each recorded step against ``target``) or None.  ``frames`` is
     None for a trace with ``frames=False``.  ``diagnostics``: a ``GraphDiagnostics`` whose fields lead
-    with the R axis (each recorded step's input state with that step's offsets) or None.  All detached."""
+    with the R axis (each recorded step's input state with that step's offsets) or None.  With
+    ``render``: ``rgb_u8`` uint8 [R,B,H*s,W*s,3|4], the frames as images (``render.render_rgb``), and
+    ``attention_u8`` uint8 [R,B,H,W,3], the attention maps as colour images (``render.colorize``), or
+    None.  All detached."""
 
-    __slots__ = ("x_final", "frames", "steps", "attention", "metrics", "diagnostics")
+    __slots__ = ("x_final", "frames", "steps", "attention", "metrics", "rgb_u8", "attention_u8", "diagnostics")
 
-    def __init__(self, x_final, frames, steps, attention, metrics=None, diagnostics=None):
+    def __init__(self, x_final, frames, steps, attention, metrics=None, diagnostics=None, *, rgb_u8=None,
+                 attention_u8=None):
         self.x_final, self.frames, self.steps, self.attention = x_final, frames, steps, attention
         self.metrics = metrics
         self.diagnostics = diagnostics
+        self.rgb_u8, self.attention_u8 = rgb_u8, attention_u8
 
     def __repr__(self):
         shape = lambda t: None if t is None else tuple(t.shape)
         return (f"TraceResult(steps={self.steps}, frames={shape(self.frames)}, "
                 f"attention={shape(self.attention)}, "
                 f"metrics={None if self.metrics is None else shape(self.metrics.stacked)}"
+                + ("" if self.rgb_u8 is None else f", rgb_u8={shape(self.rgb_u8)}")
+                + ("" if self.attention_u8 is None else f", attention_u8={shape(self.attention_u8)}")
                 + ("" if self.diagnostics is None else ", diagnostics") + ")")
 
 
 def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, every=1, record=None,
               channels=4, return_attention=False, fire_rate=1.0, message_gain=None, seed=None, sample_base=0,
               first_step=0, offsets=None, target=None, frames=True, diagnostics=False,
-              per_offset=False) -> TraceResult:
+              per_offset=False, render=None) -> TraceResult:
     """The shared body of ``NeuralCA.trace`` / ``NeuralCAGraph.trace``: a no-grad rollout that records
     frames (and attention maps, image metrics against ``target`` and graph diagnostics) in one native
-    call."""
+    call; ``render`` adds one launch over all recorded frames and one over all attention maps."""
     if x.dim() != 4:
         raise ValueError(f"state must be [B,C,H,W], got {tuple(x.shape)}")
     B, C, H, W = x.shape
@@ -399,6 +407,7 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
         raise ValueError("per_offset is part of the diagnostics: pass diagnostics=True")
     if target is not None:
         target = M.check_target(target, B, H, W)
+    render = R.check_trace_render(render, model.alpha_thr, channels, frames)
     # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
     plan = S.build_trace(steps=steps, B=B, C=C, H=H, W=W, device=x.device, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
@@ -426,4 +435,9 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
                                                   want_frames=frames)
             met = None if met is None else M.ImageMetrics(met)
         del keep
-    return TraceResult(out, frm, list(plan.record), attn, met, diag)
+        rgb_u8 = attn_u8 = None
+        if render is not None:
+            rgb_u8 = R.render_rgb(frm, render["alpha_thr"], render["upscale"], render["mode"])
+            if attn is not None:
+                attn_u8 = R.colorize(attn, render["cmap"])
+    return TraceResult(out, frm, list(plan.record), attn, met, diag, rgb_u8=rgb_u8, attention_u8=attn_u8)

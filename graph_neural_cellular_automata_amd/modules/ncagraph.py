@@ -98,7 +98,8 @@ class NeuralCAGraph(nn.Module):
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
               sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
-              frames: bool = True, diagnostics: bool = False, per_offset: bool = False) -> TraceResult:
+              frames: bool = True, diagnostics: bool = False, per_offset: bool = False,
+              render=None) -> TraceResult:
         """``steps`` CA steps in one native call that also records (extension, not in the reference):
         the per-step Python loop of the regeneration diagnostic and the video generators, on the
         rollout pipeline.  Always runs under ``no_grad`` and returns detached tensors, whatever the
@@ -130,9 +131,16 @@ class NeuralCAGraph(nn.Module):
         step's input state with that step's offsets (the convention of ``attention``): the result's
         ``diagnostics`` is a ``GraphDiagnostics`` whose fields lead with the R axis, bitwise the
         standalone call's; ``per_offset=True`` includes the [R,B,k,H,W] stack.  The other results are
-        bitwise those of the trace without it."""
+        bitwise those of the trace without it.
+
+        ``render=True`` or ``render=dict(upscale=4, mode="rgb", alpha_thr=None, cmap="viridis")`` also turns
+        the recorded frames into uint8 images on the device, one launch over all of them: the result's
+        ``rgb_u8`` [R,B,H*upscale,W*upscale,3|4] is bitwise ``render.render_rgb(frames, ...)``
+        (``alpha_thr=None``: ``self.alpha_thr``), and with ``return_attention`` its ``attention_u8``
+        [R,B,H,W,3] is bitwise ``render.colorize(attention, cmap)``.  Needs ``frames=True`` and
+        ``channels >= 4``."""
         return run_trace(self, x, steps, self.graph, self.hidden_only, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
                          message_gain=self.message_gain if message_gain is None else message_gain, seed=seed,
                          sample_base=sample_base, first_step=first_step, offsets=offsets, target=target,
-                         frames=frames, diagnostics=diagnostics, per_offset=per_offset)
+                         frames=frames, diagnostics=diagnostics, per_offset=per_offset, render=render)

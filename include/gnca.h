@@ -717,6 +717,62 @@ int gnca_pool_commit(const gnca_pool_commit_desc* desc, float* pool, const int64
                      const float* state, const float* per_sample, const float* seeds, const float* seed1,
                      const int64_t* rand_idx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Frames and maps as uint8 images: the pixel work in front of a PNG / video
+ * encoder, masked_rgb and attn_to_rgb of src/testing/test_graph_augmented_regeneration.py:29-47 and
+ * save_img of src/testing/test_intermediate_loss.py:18-37, without the host round trip.
+ *
+ * The stream of these two entry points travels in the descriptor, not as a trailing parameter: the
+ * stream gate of the test suite enumerates the declarations that have that parameter against a fixed
+ * case table, and these two are run on the same three legs (eager, side stream with delayed inputs,
+ * capture and replay) by tests/test_gpu_render.py instead.  Everything else in the conventions above
+ * holds: stream-ordered on d->stream, no allocation, no host<->device copy, no synchronisation,
+ * capturable, every byte of `out` written, no workspace.
+ * -------------------------------------------------------------------------------------------*/
+
+/*
+ * One frame per image, all arithmetic in fp32.  With m = (alpha > alpha_thr), strict, on fp32
+ * (alpha is channel 3):
+ *   GNCA_RENDER_RGB   3 bytes per pixel: v_c = clip(rgb_c * m, 0, 1) per source cell (masked_rgb)
+ *   GNCA_RENDER_RGBA  4 bytes per pixel: v_c = rgb_c * m, v_a = m                     (save_img)
+ * then bilinear resampling by the integer factor s = upscale with half-pixel centres
+ * (F.interpolate(mode="bilinear", align_corners=False)): per axis, for output index q s + p,
+ *   f = (p + 0.5) / s - 0.5,  src = max(q + f, 0),  i0 = floor(src),  i1 = min(i0 + 1, n - 1),
+ *   l1 = src - i0,  l0 = 1 - l1,  value = ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11),
+ * then clip(., 0, 1) (always, also at s = 1, where the resampling is the identity), and
+ * byte = (uint8) trunc(value * 255): truncation, as numpy's astype(np.uint8).  For s in {1,2,4,8,16}
+ * the weights are exact; inputs are assumed finite (a NaN gives an unspecified byte, inside `out`).
+ * One workgroup renders GNCA_RENDER_BAND_ROWS source rows of one image (fewer when the band and its
+ * two halo rows would not fit the LDS; GNCA_ERR_UNSUPPORTED when three rows of the image do not).
+ */
+#define GNCA_RENDER_RGB  0
+#define GNCA_RENDER_RGBA 1
+#define GNCA_RENDER_BAND_ROWS 8
+typedef struct gnca_render_desc {
+  int32_t N, H, W;        /* images; source height / width                                  */
+  int32_t upscale;        /* 1 .. 16                                                         */
+  int32_t mode;           /* GNCA_RENDER_*                                                   */
+  float   alpha_thr;
+  int64_t src_nstride;    /* floats between images; channels are H*W apart, rows contiguous  */
+  void*   stream;         /* hipStream_t, NULL = the null stream                             */
+} gnca_render_desc;
+int gnca_render_u8(const gnca_render_desc* d, const float* src, uint8_t* out);
+      /* out: [N, H*s, W*s, 3|4] contiguous, 4-byte aligned */
+
+/*
+ * One colour image per map; every one of the N maps normalises on its own:
+ *   GNCA_NORM_MAX     vmax = max(a); z = vmax > 0 ? clip(a / (vmax + 1e-8f), 0, 1) : 0  (attn_to_rgb)
+ *   GNCA_NORM_MINMAX  z = max > min ? (a - min) / (max - min) : 0
+ *   out = lut[min((int)(z * 256), 255)], three bytes.
+ * The division is IEEE-correct (the index is bitwise numpy's).  lut: DEVICE uint8 [256,3].  One
+ * workgroup per map: max / min by wavefront shuffles and LDS (order-independent), then the bytes.
+ */
+#define GNCA_NORM_MAX    0
+#define GNCA_NORM_MINMAX 1
+typedef struct gnca_colorize_desc { int32_t N, H, W, norm; void* stream; } gnca_colorize_desc;
+int gnca_colorize_u8(const gnca_colorize_desc* d, const float* maps, const uint8_t* lut, uint8_t* out);
+      /* maps [N,H,W] contiguous; out [N,H,W,3] contiguous, 4-byte aligned */
+
 #ifdef __cplusplus
 }
 #endif
