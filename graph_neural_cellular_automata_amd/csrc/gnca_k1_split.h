@@ -12,8 +12,12 @@
 // i + j <= 2 (a0b0, a0b1, a1b0, a0b2, a2b0, a1b1): the dropped terms a1b2, a2b1, a2b2 are each
 // <= 2^-24 |a||b|, the size of one fp32 rounding.  bf16 x bf16 products are exact in fp32 and
 // the MFMA accumulates in fp32.  So each GEMM is an fp32 GEMM up to a few fp32 roundings per
-// product (measured against the f64 oracle in tests/test_gpu_*.py at the same tolerances as
-// the f32 kernel).  Cost: 6 bf16 products at 1/16 the cycles of one fp32 product = 0.375 of
+// product.  Measured where it is visible, at K1's update field before GroupNorm and tanh
+// (tests/test_gpu_k1_precision.py): integer operands that single out each of the
+// six products come back exact, and on realistic operands the error against the f64 oracle is
+// that of an fp32 GEMM (1.0-1.2x torch's fp32 CPU update; a dropped third-order product would
+// be 12x).  The step-output tolerances of the other tests/test_gpu_*.py (atol 2e-6 after tanh
+// and the update gain) do not see a third-order product.  Cost: 6 bf16 products at 1/16 the cycles of one fp32 product = 0.375 of
 // the fp32 MFMA time, plus the VALU that splits the activations.
 //
 // MFMA: v_mfma_f32_32x32x16_bf16 (32 cycles, holds VALU issue for 8 of them).  Lane l: cell
@@ -279,6 +283,8 @@ __device__ __forceinline__ void ks_fill_images(const K1Args& a, char* dst, int t
 #if GNCA_K1_LEAN
     // the third part is stored halved (exact: a power-of-two scale of a bf16 value): the GEMM2
     // stack [P2/2; P2/2] adds P2.H0 / 2 to both accumulator halves, which the epilogue sums
+    // (each half may round its P2.H0 / 2 once more than a single accumulator would: integer
+    // operands come back exact below 2^23 instead of 2^24, tests/split_emul.py LIMIT)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float lo = __uint_as_float(f2[i] << 16) * 0.5f, hi = __uint_as_float(f2[i] & 0xffff0000u) * 0.5f;
