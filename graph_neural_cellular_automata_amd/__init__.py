@@ -3,8 +3,9 @@
 The HIP kernels live in csrc/ and are built into libgnca.so (C ABI: include/gnca.h).  The
 ``modules`` subpackage mirrors the reference's nn.Module API on top of it.
 """
+from .damage import DamagePolicy, regrow_trace
 from .modules import FixedSobelPerception, GraphAugmentation, NeuralCA, NeuralCAGraph
 from .render import CMAPS, colorize, render_rgb
 
 __all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph",
-           "render_rgb", "colorize", "CMAPS"]
+           "render_rgb", "colorize", "CMAPS", "DamagePolicy", "regrow_trace"]

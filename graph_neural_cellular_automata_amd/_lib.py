@@ -153,6 +153,24 @@ class ColorizeDesc(ctypes.Structure):
 
 DMG_SQUARE, DMG_CIRCLE, DMG_STRIPE_H, DMG_STRIPE_V = 0, 1, 2, 3
 DMG_ALPHA_DROP, DMG_ALPHA_DROP_SOFT, DMG_SALT_PEPPER, DMG_GAUSSIAN, DMG_HIDDEN_NOISE = 4, 5, 6, 7, 8
+DMG_STRIPES_AUTO = 9           # gnca_damage_policy only: the orientation is drawn
+DMG_MAX_KINDS = 10
+DMG_SCOPE_BATCH, DMG_SCOPE_SAMPLE = 0, 1
+DMG_SHARED_SAMPLE = 0xFFFFFFFF
+DMG_RNG_STREAMS = ("gate", "sample_gate", "kind", "size", "orient", "y", "x", "cell", "normal_u1", "normal_u2")
+
+
+class DamagePolicyDesc(ctypes.Structure):
+    """Mirror of gnca_damage_policy_desc (include/gnca.h): the stream travels in the descriptor."""
+    _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("scope", ctypes.c_int32), ("prob", ctypes.c_float), ("per_sample_prob", ctypes.c_float),
+                ("n_kinds", ctypes.c_int32), ("kinds", ctypes.c_int32 * DMG_MAX_KINDS),
+                ("cum", ctypes.c_float * DMG_MAX_KINDS), ("size_min", ctypes.c_int32), ("size_max", ctypes.c_int32),
+                ("stripe_width", ctypes.c_int32), ("alpha_thr", ctypes.c_float), ("alpha_dropout_p", ctypes.c_float),
+                ("salt_pepper_p", ctypes.c_float), ("hidden_sigma", ctypes.c_float),
+                ("gaussian_softness", ctypes.c_float), ("seed", ctypes.c_uint64), ("event", ctypes.c_int64),
+                ("sample_base", ctypes.c_int64), ("stream", ctypes.c_void_p)]
+
 
 EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_workspace_bytes", "gnca_step_f32", "gnca_step_phases_f32", "gnca_message_f32",
@@ -168,7 +186,7 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
            "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit",
            "gnca_graph_diag_workspace_bytes", "gnca_graph_diag", "gnca_rollout_trace_diag_workspace_bytes",
-           "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8")
+           "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -312,6 +330,9 @@ def load(path: str = LIB_PATH):
             lib.gnca_render_u8.argtypes = [ctypes.POINTER(RenderDesc), vp, vp]
             lib.gnca_colorize_u8.restype = ctypes.c_int
             lib.gnca_colorize_u8.argtypes = [ctypes.POINTER(ColorizeDesc), vp, vp, vp]
+        if hasattr(lib, "gnca_damage_policy"):   # (likewise)
+            lib.gnca_damage_policy.restype = ctypes.c_int
+            lib.gnca_damage_policy.argtypes = [ctypes.POINTER(DamagePolicyDesc), vp, vp, vp, vp, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

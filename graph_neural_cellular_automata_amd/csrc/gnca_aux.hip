@@ -79,6 +79,294 @@ __global__ __launch_bounds__(kThreads) void gnca_damage(const gnca_damage_desc d
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The damage policy with its draws on the device (gnca_damage_policy; include/gnca.h holds the
+// RNG's definition and the draw rules).  Per cell the arithmetic is gnca_damage's above, kept in
+// step with it expression by expression: tests/test_gpu_damage_policy.py compares the two bitwise.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t dmg_key(uint64_t k1, uint64_t sample, int stream) {
+  return mix64(k1 ^ ((sample << 8) | (uint64_t)stream));
+}
+
+__device__ __forceinline__ uint32_t dmg_draw(uint64_t k2, uint64_t index) {
+  return (uint32_t)(mix64(k2 + index) >> 40);
+}
+
+__device__ __forceinline__ float dmg_uniform(uint32_t d) { return (float)d * (1.0f / 16777216.0f); }
+
+// integer in [lo, hi] (hi >= lo)
+__device__ __forceinline__ int dmg_randint(uint32_t d, int lo, int hi) {
+  return lo + (int)(((uint64_t)d * (uint64_t)((int64_t)hi - lo + 1)) >> 24);
+}
+
+__device__ __forceinline__ float dmg_normal(uint32_t d1, uint32_t d2) {
+  const float u1 = (float)(d1 + 1u) * (1.0f / 16777216.0f);
+  const float u2 = (float)d2 * (1.0f / 16777216.0f);
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// One sample's scalar draws: (applied, primitive kind, size argument, y, x) are gnca_damage's kind,
+// size and pos[b].  Depends on the workgroup's sample only, so it stays on the scalar unit.
+struct DmgDraws {
+  int applied, prim, arg, y, x;
+};
+
+__device__ __forceinline__ DmgDraws dmg_sample_draws(const gnca_damage_policy_desc& d, uint64_t k1, int b,
+                                                     const int32_t* forced) {
+  DmgDraws s = {0, -1, 0, 0, 0};
+  const uint64_t gs = (uint64_t)(d.sample_base + b);
+  const bool per_sample = d.scope == GNCA_DMG_SCOPE_SAMPLE;
+  const uint64_t ks = per_sample ? gs : GNCA_DMG_SHARED_SAMPLE;   // the key of the scalar draws
+  int kind = -1;
+  if (forced != nullptr) {
+    kind = forced[b];
+    if (kind < GNCA_DMG_SQUARE || kind > GNCA_DMG_STRIPES_AUTO) return s;
+  } else {
+    if (!(dmg_uniform(dmg_draw(dmg_key(k1, GNCA_DMG_SHARED_SAMPLE, GNCA_DMG_RNG_GATE), 0)) <= d.prob)) return s;
+    if (per_sample && !(dmg_uniform(dmg_draw(dmg_key(k1, gs, GNCA_DMG_RNG_SAMPLE_GATE), 0)) <= d.per_sample_prob))
+      return s;
+    const float uk = dmg_uniform(dmg_draw(dmg_key(k1, ks, GNCA_DMG_RNG_KIND), 0));
+#pragma unroll
+    for (int k = GNCA_DMG_MAX_KINDS - 1; k >= 0; --k)   // ends on the smallest k with uk < cum[k]
+      if (k < d.n_kinds && (uk < d.cum[k] || k == d.n_kinds - 1)) kind = d.kinds[k];
+  }
+  const int size = dmg_randint(dmg_draw(dmg_key(k1, ks, GNCA_DMG_RNG_SIZE), 0), d.size_min, d.size_max);
+  const int H = d.H, W = d.W;
+  switch (kind) {
+    case GNCA_DMG_SQUARE:
+      if (size <= 0) return s;
+      s.arg = size;
+      s.y = dmg_randint(dmg_draw(dmg_key(k1, gs, GNCA_DMG_RNG_Y), 0), 0, max(1, H - size + 1) - 1);
+      s.x = dmg_randint(dmg_draw(dmg_key(k1, gs, GNCA_DMG_RNG_X), 0), 0, max(1, W - size + 1) - 1);
+      break;
+    case GNCA_DMG_CIRCLE:
+    case GNCA_DMG_GAUSSIAN: {
+      const int r = size > 1 ? size / 2 : 1;
+      s.arg = r;
+      s.y = dmg_randint(dmg_draw(dmg_key(k1, gs, GNCA_DMG_RNG_Y), 0), r, max(r + 1, H - r) - 1);
+      s.x = dmg_randint(dmg_draw(dmg_key(k1, gs, GNCA_DMG_RNG_X), 0), r, max(r + 1, W - r) - 1);
+      break;
+    }
+    case GNCA_DMG_STRIPE_H:
+    case GNCA_DMG_STRIPE_V:
+    case GNCA_DMG_STRIPES_AUTO: {
+      const int width = d.stripe_width > 0 ? d.stripe_width : size;
+      if (width <= 0) return s;
+      s.arg = width;
+      if (kind == GNCA_DMG_STRIPES_AUTO)
+        kind = dmg_draw(dmg_key(k1, ks, GNCA_DMG_RNG_ORIENT), 0) < (1u << 23) ? GNCA_DMG_STRIPE_H : GNCA_DMG_STRIPE_V;
+      if (kind == GNCA_DMG_STRIPE_H)
+        s.y = dmg_randint(dmg_draw(dmg_key(k1, ks, GNCA_DMG_RNG_Y), 0), 0, max(1, H - width + 1) - 1);
+      else
+        s.x = dmg_randint(dmg_draw(dmg_key(k1, ks, GNCA_DMG_RNG_X), 0), 0, max(1, W - width + 1) - 1);
+      break;
+    }
+    case GNCA_DMG_ALPHA_DROP:
+    case GNCA_DMG_ALPHA_DROP_SOFT:
+      if (d.alpha_dropout_p <= 0.f) return s;
+      break;
+    case GNCA_DMG_SALT_PEPPER:
+      if (d.salt_pepper_p <= 0.f) return s;
+      break;
+    case GNCA_DMG_HIDDEN_NOISE:
+      if (d.C <= 4 || d.hidden_sigma <= 0.f) return s;
+      break;
+    default:
+      return s;
+  }
+  s.applied = 1;
+  s.prim = kind;
+  return s;
+}
+
+__host__ __device__ inline int dmg_clampi(long v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
+
+// Workgroup (band, sample): rows [band * band_rows, ...) of sample blockIdx.x / nbands.  V = 4: 16-byte
+// accesses along W (W % 4 == 0 and 16-byte aligned bases), V = 1 otherwise.  Only the rows and vector
+// columns of the kind's bounding box are visited; a multiplicative kind reads and writes only the
+// vectors that hold a cell whose factor is not 1, and changes only those cells.
+template <int V>
+__global__ __launch_bounds__(kThreads) void gnca_damage_policy_k(const gnca_damage_policy_desc d, int band_rows,
+                                                                 int nbands, float* state, const int32_t* forced,
+                                                                 const int64_t* event_dev, int32_t* draws_out,
+                                                                 float* noise_out) {
+  typedef float vf __attribute__((ext_vector_type(V)));
+  const int tid = threadIdx.x;
+  const int b = (int)(blockIdx.x / (unsigned)nbands), band = (int)(blockIdx.x % (unsigned)nbands);
+  const int C = d.C, H = d.H, W = d.W;
+  const size_t HW = (size_t)H * W;
+  const int64_t event = event_dev != nullptr ? event_dev[0] : d.event;
+  const uint64_t k0 = mix64(d.seed + 0xD6E8FEB86659FD93ull);
+  const uint64_t k1 = mix64(k0 + 0x9E3779B97F4A7C15ull * (uint64_t)(event + 1));
+  const DmgDraws s = dmg_sample_draws(d, k1, b, forced);
+  if (band == 0 && draws_out != nullptr && tid < 8) {
+    const int v = tid == 0 ? s.applied : tid == 1 ? s.prim : tid == 2 ? s.arg : tid == 3 ? s.y : tid == 4 ? s.x : 0;
+    draws_out[(size_t)8 * b + tid] = v;
+  }
+  if (!s.applied) return;
+
+  // the kind's bounding box [y0, y1) x [x0, x1), clipped to the field
+  const int sz = s.arg, py = s.y, px = s.x;
+  long y0 = 0, y1 = H, x0 = 0, x1 = W;
+  switch (s.prim) {
+    case GNCA_DMG_SQUARE:   y0 = py; y1 = (long)py + sz; x0 = px; x1 = (long)px + sz; break;
+    case GNCA_DMG_CIRCLE:   y0 = (long)py - sz; y1 = (long)py + sz + 1; x0 = (long)px - sz; x1 = (long)px + sz + 1; break;
+    case GNCA_DMG_STRIPE_H: y0 = py; y1 = (long)py + sz; break;
+    case GNCA_DMG_STRIPE_V: x0 = px; x1 = (long)px + sz; break;
+    case GNCA_DMG_GAUSSIAN: {
+      // damp = 1 - exp(-r2 / (2 s^2)) rounds to 1 once the exponent passes 25 ln 2 = 17.33: outside
+      // |dy|, |dx| <= 6 s + 2 (exponent > 18) every factor is exactly 1
+      const float ext = 6.f * ((float)sz * fmaxf(1e-6f, d.gaussian_softness)) + 2.f;
+      if (ext < 1e9f) {
+        const long e = (long)ext;
+        y0 = (long)py - e; y1 = (long)py + e + 1; x0 = (long)px - e; x1 = (long)px + e + 1;
+      }
+      break;
+    }
+    default: break;
+  }
+  const int r0 = band * band_rows;
+  const int lo = max(r0, dmg_clampi(y0, 0, H)), hi = min(min(r0 + band_rows, H), dmg_clampi(y1, 0, H));
+  const int cx0 = dmg_clampi(x0, 0, W), cx1 = dmg_clampi(x1, 0, W);
+  if (lo >= hi || cx0 >= cx1) return;
+  const int vx0 = cx0 / V, nvx = (cx1 + V - 1) / V - vx0;
+  const int total = (hi - lo) * nvx;
+
+  const uint64_t gsmp = (uint64_t)(d.sample_base + b);
+  const uint64_t kc = dmg_key(k1, gsmp, GNCA_DMG_RNG_CELL);
+  const uint64_t kn1 = dmg_key(k1, gsmp, GNCA_DMG_RNG_NORMAL_U1), kn2 = dmg_key(k1, gsmp, GNCA_DMG_RNG_NORMAL_U2);
+  const int NP = C > 4 ? C - 4 : 1;
+  float* sample = state + (size_t)b * C * HW;
+  float* nz = noise_out != nullptr ? noise_out + (size_t)b * NP * HW : nullptr;
+
+  for (int t = tid; t < total; t += kThreads) {
+    const int i = lo + t / nvx, j0 = (vx0 + t % nvx) * V;
+    const size_t cell = (size_t)i * W + j0;
+    float* sb = sample + cell;
+    switch (s.prim) {
+      case GNCA_DMG_SQUARE:
+      case GNCA_DMG_CIRCLE:
+      case GNCA_DMG_STRIPE_H:
+      case GNCA_DMG_STRIPE_V: {
+        bool in[V];
+        int n = 0;
+#pragma unroll
+        for (int l = 0; l < V; ++l) {
+          const int j = j0 + l;
+          if (s.prim == GNCA_DMG_SQUARE) {
+            in[l] = i >= py && i < py + sz && j >= px && j < px + sz;
+          } else if (s.prim == GNCA_DMG_CIRCLE) {
+            const float dy = (float)i - (float)py, dx = (float)j - (float)px;
+            in[l] = dy * dy + dx * dx <= (float)(sz * sz);
+          } else if (s.prim == GNCA_DMG_STRIPE_H) {
+            in[l] = i >= py && i < py + sz;
+          } else {
+            in[l] = j >= px && j < px + sz;
+          }
+          n += in[l] ? 1 : 0;
+        }
+        if (n == V) {
+          vf z;
+#pragma unroll
+          for (int l = 0; l < V; ++l) z[l] = 0.f;
+          for (int c = 0; c < C; ++c) *reinterpret_cast<vf*>(sb + c * HW) = z;
+        } else if (n > 0) {
+#pragma unroll
+          for (int l = 0; l < V; ++l)
+            if (in[l])
+              for (int c = 0; c < C; ++c) sb[c * HW + l] = 0.f;
+        }
+        break;
+      }
+      case GNCA_DMG_GAUSSIAN: {
+        float f[V];
+        bool any = false;
+#pragma unroll
+        for (int l = 0; l < V; ++l) {
+          const float dy = (float)i - (float)py, dx = (float)(j0 + l) - (float)px;
+          const float r2 = dy * dy + dx * dx;
+          const float sg = (float)sz * fmaxf(1e-6f, d.gaussian_softness);
+          const float m = expf(-(r2 / (2.f * sg * sg)));
+          f[l] = fminf(fmaxf(1.f - m, 0.f), 1.f);
+          any = any || f[l] != 1.f;
+        }
+        if (!any) break;
+        for (int c = 0; c < C; ++c) {
+          vf x = *reinterpret_cast<const vf*>(sb + c * HW);
+#pragma unroll
+          for (int l = 0; l < V; ++l)
+            if (f[l] != 1.f) x[l] *= f[l];
+          *reinterpret_cast<vf*>(sb + c * HW) = x;
+        }
+        break;
+      }
+      case GNCA_DMG_ALPHA_DROP:
+      case GNCA_DMG_ALPHA_DROP_SOFT:
+      case GNCA_DMG_SALT_PEPPER: {
+        const float p = s.prim == GNCA_DMG_SALT_PEPPER ? d.salt_pepper_p : d.alpha_dropout_p;
+        vf u;
+        bool hit[V];
+        bool any = false;
+#pragma unroll
+        for (int l = 0; l < V; ++l) {
+          u[l] = dmg_uniform(dmg_draw(kc, cell + l));
+          hit[l] = u[l] < p;
+          any = any || hit[l];
+        }
+        if (nz != nullptr) *reinterpret_cast<vf*>(nz + cell) = u;
+        if (!any) break;
+        vf a = *reinterpret_cast<const vf*>(sb + 3 * HW);
+        if (s.prim == GNCA_DMG_SALT_PEPPER) {
+#pragma unroll
+          for (int l = 0; l < V; ++l)
+            if (hit[l]) a[l] *= 0.f;   // (1 - 1): the sign of zero kept
+          *reinterpret_cast<vf*>(sb + 3 * HW) = a;
+          break;
+        }
+        any = false;
+#pragma unroll
+        for (int l = 0; l < V; ++l) {
+          hit[l] = hit[l] && a[l] > d.alpha_thr;
+          any = any || hit[l];
+        }
+        if (!any) break;
+        if (s.prim == GNCA_DMG_ALPHA_DROP) {   // hard: every channel *= (1 - drop), the sign of zero kept
+          for (int c = 0; c < C; ++c) {
+            vf x = *reinterpret_cast<const vf*>(sb + c * HW);
+#pragma unroll
+            for (int l = 0; l < V; ++l)
+              if (hit[l]) x[l] *= 0.f;
+            *reinterpret_cast<vf*>(sb + c * HW) = x;
+          }
+        } else {
+#pragma unroll
+          for (int l = 0; l < V; ++l)
+            if (hit[l]) a[l] = a[l] * 0.f;
+          *reinterpret_cast<vf*>(sb + 3 * HW) = a;
+        }
+        break;
+      }
+      case GNCA_DMG_HIDDEN_NOISE:
+        for (int c = 4; c < C; ++c) {
+          vf x = *reinterpret_cast<const vf*>(sb + c * HW);
+          vf nn;
+          const uint64_t idx = (uint64_t)(c - 4) * HW + cell;
+#pragma unroll
+          for (int l = 0; l < V; ++l) {
+            nn[l] = dmg_normal(dmg_draw(kn1, idx + l), dmg_draw(kn2, idx + l));
+            const float v = x[l] + nn[l] * d.hidden_sigma;
+            x[l] = fminf(fmaxf(v, 0.f), 1.f);
+          }
+          *reinterpret_cast<vf*>(sb + c * HW) = x;
+          if (nz != nullptr) *reinterpret_cast<vf*>(nz + idx) = nn;
+        }
+        break;
+      default:
+        break;
+    }
+  }
+}
+
 // loss_premult_rgba (train_graph_augmented_nca.py:52-61): one workgroup per sample, fixed-order
 // fp64 reduction (deterministic)
 __global__ __launch_bounds__(kThreads) void gnca_loss_fwd(int H, int W, const float* pred, long pbs,
@@ -790,6 +1078,36 @@ extern "C" int gnca_damage_f32(const gnca_damage_desc* d, float* state, const in
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(gnca_damage, dim3((unsigned)blocks), dim3(kThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), *d, state, pos, noise);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    g_last_hip = (int)e;
+    return GNCA_ERR_HIP;
+  }
+  return GNCA_OK;
+}
+
+extern "C" int gnca_damage_policy(const gnca_damage_policy_desc* d, float* state, const int32_t* forced_kind,
+                                  const int64_t* event_dev, int32_t* draws_out, float* noise_out) {
+  if (!d || !state || d->B < 0 || d->C < 4 || d->H <= 0 || d->W <= 0) return GNCA_ERR_INVALID;
+  if (d->scope != GNCA_DMG_SCOPE_BATCH && d->scope != GNCA_DMG_SCOPE_SAMPLE) return GNCA_ERR_INVALID;
+  if (d->n_kinds < 1 || d->n_kinds > GNCA_DMG_MAX_KINDS || d->size_max < d->size_min) return GNCA_ERR_INVALID;
+  for (int k = 0; k < d->n_kinds; ++k)
+    if (d->kinds[k] < GNCA_DMG_SQUARE || d->kinds[k] > GNCA_DMG_STRIPES_AUTO) return GNCA_ERR_INVALID;
+  if (d->B == 0) return GNCA_OK;
+  const bool vec = d->W % 4 == 0 && ((uintptr_t)state & 15) == 0 && ((uintptr_t)noise_out & 15) == 0;
+  const int vpr = vec ? d->W / 4 : d->W;               // vectors per row
+  int band_rows = (kThreads + vpr - 1) / vpr;          // about one vector per thread and channel
+  if (band_rows > d->H) band_rows = d->H;
+  const int nbands = (d->H + band_rows - 1) / band_rows;
+  if ((long)d->B * nbands > 0x7fffffffL) return GNCA_ERR_INVALID;
+  const dim3 grid((unsigned)((long)d->B * nbands));
+  hipStream_t st = reinterpret_cast<hipStream_t>(d->stream);
+  if (vec)
+    hipLaunchKernelGGL(gnca_damage_policy_k<4>, grid, dim3(kThreads), 0, st, *d, band_rows, nbands, state, forced_kind,
+                       event_dev, draws_out, noise_out);
+  else
+    hipLaunchKernelGGL(gnca_damage_policy_k<1>, grid, dim3(kThreads), 0, st, *d, band_rows, nbands, state, forced_kind,
+                       event_dev, draws_out, noise_out);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     g_last_hip = (int)e;

@@ -32,6 +32,7 @@
  *                        src/training/train_graph_augmented_nca.py:305-321,
  *                        src/testing/test_graph_augmented_regeneration.py:183-194
  *   gnca_damage_f32      the damage curriculum's batch ops, src/utils/damage.py:15-138
+ *   gnca_damage_policy   apply_damage_policy_ with its draws, src/utils/damage.py:99-138
  *   gnca_step_bwd_f32    torch autograd's backward through NeuralCAGraph.forward /
  *                        NeuralCA.forward, i.e. the per-step part of the trainers'
  *                        loss.backward() (BPTT): src/training/train_graph_augmented_nca.py:369,
@@ -556,6 +557,108 @@ typedef struct gnca_damage_desc {
  */
 int gnca_damage_f32(const gnca_damage_desc* desc, float* state, const int32_t* pos,
                     const float* noise, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The damage POLICY on the device (src/utils/damage.py:99-138): whether to damage, which kind, its
+ * size, orientation, positions and per-cell noise are all drawn INSIDE one launch from a counter
+ * RNG, so the call needs no host draw, no noise tensor and no host wait, and a kind per sample is
+ * possible.  In place on the [B,C,H,W] state.  Per cell the arithmetic of every kind is that of
+ * gnca_damage_f32 (same expressions, same order).
+ *
+ * RNG (the definition; every value is an integer, so a restatement in any language is bitwise).
+ * With mix64(z) = { z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB;
+ * return z ^ z>>31; } in uint64 arithmetic:
+ *   k0 = mix64(seed + 0xD6E8FEB86659FD93)          (a domain constant of its own: `seed` may be the
+ *   k1 = mix64(k0 + 0x9E3779B97F4A7C15 * (uint64)(event + 1))        fire hash's rng_seed)
+ *   k2 = mix64(k1 ^ (sample << 8 | stream))
+ *   d(seed, event, sample, stream, index) = mix64(k2 + index) >> 40            in [0, 2^24)
+ * `sample` is the GLOBAL sample index sample_base + b, or GNCA_DMG_SHARED_SAMPLE for a draw the whole
+ * batch (every rank of a sharded batch) shares; `stream` is a GNCA_DMG_RNG_* id; `index` is 0 for a
+ * scalar draw, the cell index i * W + j for a cell uniform and (c - 4) * H * W + i * W + j for the
+ * normal of hidden channel c.
+ *   uniform            u = d * 2^-24 (exact in fp32)
+ *   integer in [lo,hi] lo + ((d * (hi - lo + 1)) >> 24), in 64-bit integers
+ *   gate               pass iff u <= prob
+ *   kind               kinds[k] of the smallest k < n_kinds with u < cum[k] (k = n_kinds - 1 if none)
+ *   orientation        horizontal iff d < 2^23
+ *   normal             sqrtf(-2 * logf((d1 + 1) * 2^-24)) * cosf(2 pi * (d2 * 2^-24)), d1 / d2 from the
+ *                      streams NORMAL_U1 / NORMAL_U2 at the same index (fp32, library logf/sqrtf/cosf)
+ *
+ * What is drawn.  size = integer in [size_min, size_max] (stream SIZE).  Then by kind:
+ *   SQUARE        side = size; origin y in [0, max(1, H-side+1)), x in [0, max(1, W-side+1))
+ *   CIRCLE        r = size > 1 ? size / 2 : 1; centre y in [r, max(r+1, H-r)), x in [r, max(r+1, W-r))
+ *   GAUSSIAN      r as the circle's, centre as the circle's
+ *   STRIPE_H / _V width = stripe_width > 0 ? stripe_width : size; origin y in [0, max(1, H-width+1))
+ *                 (x = 0), or x in [0, max(1, W-width+1)) (y = 0)
+ *   STRIPES_AUTO  the orientation is drawn (stream ORIENT), then as STRIPE_H / STRIPE_V
+ *   ALPHA_DROP, ALPHA_DROP_SOFT (p = alpha_dropout_p), SALT_PEPPER (p = salt_pepper_p): a uniform per cell
+ *   HIDDEN_NOISE  a normal per hidden channel and cell, scaled by hidden_sigma
+ * y comes from stream Y and x from stream X.  A sample is left untouched (the reference's early
+ * returns) for a side or width <= 0, p <= 0, hidden_sigma <= 0 and hidden noise at C <= 4.
+ *
+ * scope GNCA_DMG_SCOPE_BATCH (the reference's structure): the gate (stream GATE, u <= prob), the kind,
+ * the size, the stripe orientation and the stripe origin are drawn once, with sample =
+ * GNCA_DMG_SHARED_SAMPLE; the positions of square / circle / gaussian per global sample; the cell noise
+ * per (global sample, cell).  per_sample_prob is not read.
+ * scope GNCA_DMG_SCOPE_SAMPLE: the batch gate as above, then per global sample a gate (stream
+ * SAMPLE_GATE, u <= per_sample_prob) and every other draw.
+ * Either way a batch of B samples at sample_base s is bitwise rows [s, s+B) of a larger batch.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_DMG_STRIPES_AUTO 9  /* stripe_wipe_ "auto" (the policy's "stripes"): orientation drawn */
+#define GNCA_DMG_MAX_KINDS   10
+
+#define GNCA_DMG_SCOPE_BATCH  0
+#define GNCA_DMG_SCOPE_SAMPLE 1
+
+#define GNCA_DMG_SHARED_SAMPLE 0xFFFFFFFFull
+
+#define GNCA_DMG_RNG_GATE        0
+#define GNCA_DMG_RNG_SAMPLE_GATE 1
+#define GNCA_DMG_RNG_KIND        2
+#define GNCA_DMG_RNG_SIZE        3
+#define GNCA_DMG_RNG_ORIENT      4
+#define GNCA_DMG_RNG_Y           5
+#define GNCA_DMG_RNG_X           6
+#define GNCA_DMG_RNG_CELL        7
+#define GNCA_DMG_RNG_NORMAL_U1   8
+#define GNCA_DMG_RNG_NORMAL_U2   9
+
+typedef struct gnca_damage_policy_desc {
+  int32_t B, C, H, W;
+  int32_t scope;               /* GNCA_DMG_SCOPE_*                                              */
+  float prob;                  /* the batch gate                                                */
+  float per_sample_prob;       /* the per-sample gate (GNCA_DMG_SCOPE_SAMPLE)                    */
+  int32_t n_kinds;             /* 1..GNCA_DMG_MAX_KINDS                                         */
+  int32_t kinds[GNCA_DMG_MAX_KINDS];   /* GNCA_DMG_* codes 0..9                                 */
+  float cum[GNCA_DMG_MAX_KINDS];       /* fp32 of the running weight sums / their total (fp64 on the
+                                          host); the last one 1.0                               */
+  int32_t size_min, size_max;
+  int32_t stripe_width;        /* <= 0: the drawn size                                          */
+  float alpha_thr, alpha_dropout_p, salt_pepper_p, hidden_sigma, gaussian_softness;
+  uint64_t seed;
+  int64_t event;               /* the draw counter: one value per policy call                   */
+  int64_t sample_base;         /* global index of sample 0 (sharded batches)                    */
+  void* stream;                /* hipStream_t; NULL = the default stream                        */
+} gnca_damage_policy_desc;
+
+/*
+ * One launch, stream-ordered on desc->stream; no allocation, no copy, no synchronisation (it can be
+ * captured into a graph).  The stream travels in the descriptor.
+ * forced_kind: int32 [B] device or NULL.  forced_kind[b] in 0..9 replaces the gates and the kind draw
+ *              of sample b (the other draws stay as above); any other value leaves sample b untouched.
+ * event_dev:   one int64 on the device or NULL; when given it replaces desc->event and is read by the
+ *              kernel, so a captured loop that increments it draws afresh on every replay.
+ * draws_out:   int32 [B,8] device or NULL: {applied, primitive kind, size argument, y, x, 0, 0, 0} per
+ *              sample, where (primitive kind 0..8, size argument, (y, x)) are gnca_damage_f32's kind,
+ *              size and pos[b] for the same effect; an untouched sample gets {0, -1, 0, 0, 0, 0, 0, 0}.
+ * noise_out:   fp32 [B, max(1, C-4), H, W] device or NULL: the uniforms in plane 0 of a sample with an
+ *              alpha kind, the normals in all C-4 planes of a hidden-noise sample (gnca_damage_f32's
+ *              `noise`); every other element is NOT written.
+ * GNCA_ERR_INVALID: null desc / state, B < 0, C < 4, H or W <= 0, a scope or kind code out of range,
+ * n_kinds outside 1..GNCA_DMG_MAX_KINDS, size_max < size_min.  B == 0 is GNCA_OK (nothing to do).
+ */
+int gnca_damage_policy(const gnca_damage_policy_desc* desc, float* state, const int32_t* forced_kind,
+                       const int64_t* event_dev, int32_t* draws_out, float* noise_out);
 
 /*
  * The graph trainer's loss (src/training/train_graph_augmented_nca.py:52-61), fused:
