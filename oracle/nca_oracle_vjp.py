@@ -55,12 +55,21 @@ def _sum_outer(g: np.ndarray, z: np.ndarray) -> np.ndarray:
     return np.einsum("bohw,bihw->oi", g, z, optimize=True)
 
 
-def nca_step_vjp(x: np.ndarray, p: dict, cfg: dict, gy: np.ndarray, *, chosen=None, fire_mask=None):
+def nca_step_vjp(x: np.ndarray, p: dict, cfg: dict, gy: np.ndarray, *, chosen=None, fire_mask=None,
+                 post_alive=None, return_update=False):
     """Gradients of ``sum(nca_step(x) * gy)`` w.r.t. ``x`` and the trainable parameters.
 
     Returns ``(gx, grads)``; ``grads`` maps state_dict keys to arrays of the parameter's shape.
     Keys of parameters the reference leaves without a gradient are absent (no graph call, or
     no offsets drawn).
+
+    ``post_alive``: a [B,1,H,W] {0,1} array that replaces the post-update alive mask computed
+    here.  Masks are constants of the VJP and this one is used once (the alpha gate), so nothing
+    else changes; a caller that knows the mask from elsewhere (a float32 run whose updated alpha
+    sits within rounding of the threshold) passes it.
+    ``return_update``: return ``(gx, grads, xt, post)`` with the updated state BEFORE the post gate
+    (``nca_oracle.nca_update``'s state, whose pooled alpha the post mask thresholds) and the post
+    mask computed here, whether or not ``post_alive`` replaced it.
     """
     dt = x.dtype
     B, C, H, W = x.shape
@@ -129,7 +138,8 @@ def nca_step_vjp(x: np.ndarray, p: dict, cfg: dict, gy: np.ndarray, *, chosen=No
     # ---------------- backward ----------------------------------------------------------
     grads = {}
     g_xt = gy.astype(dt).copy()
-    g_xt[:, 3:4] *= post                                                # (:158-166)
+    gate = post if post_alive is None else np.asarray(post_alive, dt).reshape(post.shape)
+    g_xt[:, 3:4] *= gate                                                # (:158-166)
     gx = g_xt.copy()                                                    # residual x + ...
     g_xn = g_xt * dt.type(cfg["update_gain"]) * (1 - t * t)             # (:154)
     if use_gn:                                                          # (:153) GroupNorm(1,C)
@@ -189,4 +199,6 @@ def nca_step_vjp(x: np.ndarray, p: dict, cfg: dict, gy: np.ndarray, *, chosen=No
         grads["graph.query_proj.bias"] = g_Q.sum(axis=(0, 2, 3))
         grads["graph.key_proj.weight"] = _sum_outer(g_K, x).reshape(p["graph.key_proj.weight"].shape)
         grads["graph.key_proj.bias"] = g_K.sum(axis=(0, 2, 3))
+    if return_update:
+        return gx, grads, xt, post
     return gx, grads

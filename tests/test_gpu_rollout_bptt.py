@@ -6,8 +6,11 @@ Bounds.  Fixtures: the project's own for this loop (test_gpu_grad.py: loss 1e-5 
 state 1e-4, gradients 5e-5 * max|ref| + 1e-9).  Against the per-step path: x_final and gx do not
 depend on the cross-step reduction order, so they are bitwise equal; a weight gradient G is compared
 with R, the float64 sum of the per-step path's per-step gradients, within RT * max|R| + AT (RT, AT
-of test_gpu_grad.py: one step's bound, assumed to hold for the fp32 accumulation over these T <= 4
-steps; each case prints the rollout's and the per-step path's own error against R before asserting).
+of test_gpu_grad.py: one step's bound, applied to the fp32 accumulation over these T <= 4 steps;
+each case prints the rollout's and the per-step path's own error against R before asserting).  The
+bound at the trainers' lengths (24-72 steps of a state grown from a seed cell) is derived and
+checked in tests/test_gpu_bptt_long.py, which also measures this one there: it holds with a factor
+of a hundred to spare.
 """
 import random
 
