@@ -2382,7 +2382,7 @@ const char* gnca_status_string(int s) {
   switch (s) {
     case GNCA_OK: return "ok";
     case GNCA_ERR_INVALID: return "invalid argument";
-    case GNCA_ERR_UNSUPPORTED: return "unsupported shape class (C must be <= 32, hidden <= 256)";
+    case GNCA_ERR_UNSUPPORTED: return "unsupported shape class (4 <= C <= 32; hidden <= 128, or <= 256 for 13 <= C <= 16)";
     case GNCA_ERR_WORKSPACE: return "workspace too small";
     case GNCA_ERR_HIP: return "HIP launch failed";
     default: return "unknown status";

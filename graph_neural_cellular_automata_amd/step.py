@@ -110,6 +110,9 @@ def make_weights(tensors: dict) -> tuple[L.Weights, list]:
 
 _WS_BYTES: dict = {}
 
+# the shape classes libgnca.so is compiled for (find_variant in gnca_step.hip)
+SUPPORT_SET = "supported: 4 <= C <= 32; hidden <= 128, or hidden <= 256 for 13 <= C <= 16"
+
 
 def workspace(desc: L.StepDesc, device) -> torch.Tensor:
     # the size depends on the shape class and the offsets' radius (the tile plan), not on the
@@ -127,7 +130,7 @@ def workspace(desc: L.StepDesc, device) -> torch.Tensor:
     if n == 0:
         raise L.GncaError(
             f"unsupported step shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-            f"hidden={desc.hidden} (compiled for C <= 32, hidden <= 256)")
+            f"hidden={desc.hidden} ({SUPPORT_SET})")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
@@ -334,7 +337,7 @@ def step_backward(desc, weights, x, gy, fire=None, want: dict | None = None, sav
     if n == 0:
         raise L.GncaError(
             f"unsupported step shape for the backward: B={desc.B} C={desc.C} H={desc.H} "
-            f"W={desc.W} hidden={desc.hidden}")
+            f"W={desc.W} hidden={desc.hidden} ({SUPPORT_SET})")
     ws = torch.empty(n, dtype=torch.uint8, device=x.device)
     act = _active_u8(active, desc.B, x.device)
     rc = lib.gnca_step_bwd_f32(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), _ptr(fire),
@@ -560,7 +563,7 @@ def trace(desc, weights, x, steps: int, offsets_per_step: list, record: list, ch
     n = lib.gnca_rollout_trace_workspace_bytes(ctypes.byref(desc), ctypes.byref(a))
     if n == 0:
         raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden}")
+                          f"hidden={desc.hidden} ({SUPPORT_SET})")
     ws = torch.empty(n, dtype=torch.uint8, device=x.device)
     rc = lib.gnca_rollout_trace_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), x.data_ptr(),
                                     out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
@@ -624,7 +627,7 @@ def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels,
     n = size(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
     if n == 0:
         raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden}")
+                          f"hidden={desc.hidden} ({SUPPORT_SET})")
     ws = torch.empty(n, dtype=torch.uint8, device=x.device)
     if fn is None:
         rc = lib.gnca_rollout_trace_metrics_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a),
@@ -750,7 +753,8 @@ class RolloutCall:
         n = fn(ctypes.byref(self.desc), ctypes.byref(self.c))
         if n == 0:
             d = self.desc
-            raise L.GncaError(f"unsupported rollout shape: B={d.B} C={d.C} H={d.H} W={d.W} hidden={d.hidden}")
+            raise L.GncaError(f"unsupported rollout shape: B={d.B} C={d.C} H={d.H} W={d.W} hidden={d.hidden} "
+                              f"({SUPPORT_SET})")
         return n
 
     def forward(self, weights, x, want_tape: bool):

@@ -81,7 +81,8 @@ extern "C" {
 typedef enum gnca_status {
   GNCA_OK = 0,
   GNCA_ERR_INVALID = -1,      /* bad shape / argument / null pointer                      */
-  GNCA_ERR_UNSUPPORTED = -2,  /* shape class not compiled in (C > 32, hidden > 256, ...)  */
+  GNCA_ERR_UNSUPPORTED = -2,  /* shape class not compiled in: needs 4 <= C <= 32 and
+                                 hidden <= 128 (<= 256 for 13 <= C <= 16)                 */
   GNCA_ERR_WORKSPACE = -3,    /* workspace too small (see gnca_workspace_bytes)            */
   GNCA_ERR_HIP = -4           /* a HIP launch failed; gnca_last_hip_error() has the code   */
 } gnca_status;

@@ -94,6 +94,11 @@ class TorchCpuStep:
 
     @torch.no_grad()
     def __call__(self, x, fire_rate: float = 1.0, chosen=None, fire_mask=None):
+        return self.step(x, fire_rate, chosen, fire_mask)
+
+    def step(self, x, fire_rate: float = 1.0, chosen=None, fire_mask=None):
+        """The step without ``no_grad``: autograd through it gives the fp32 VJP (the tests set
+        ``requires_grad`` on ``x`` and on the tensors of ``self.p``)."""
         p, C = self.p, self.C
         B, _, H, W = x.shape
         y = F.conv2d(x, p["perception.conv.weight"], padding=1, groups=C)

@@ -4,6 +4,7 @@ Run in the build container only (it needs /root/reference, which does not exist 
 box):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py --shape-classes   # those three only
 
 Each fixture is data only: the input state, the model weights (a state_dict flattened into
 ``w:<key>`` arrays), the knobs, the offsets ``random.sample`` drew, the fire mask
@@ -277,7 +278,33 @@ def main():
     kcl = dict(BASE, C=12, Hd=48, use_groupnorm=False)
     save_case("classic_c12_hd48_nogn_b2_20", make_classic(kcl, None, 10), kcl,
               blob_state(2, 12, 20, 20, gen), 0.5, graph=False)
+    shape_class_cases()
+
+
+SHAPE_CLASS_SEED = 4100
+
+
+def shape_class_knobs():
+    """name -> (knobs, init seed, canvas) of the fixtures whose channel count is no multiple of 4 (the
+    kernels pad it to CP = 8 / 16 / 8): shared with make_golden_grad.py."""
+    return {
+        "graph_torus_c6_hd40_b2_12x16": (dict(BASE, C=6, Hd=40, d=8, r=2, K=4, hidden_only=False, scaling=0.5), 21,
+                                         (12, 16)),
+        "graph_zeropad_c13_hd128_b2_16": (dict(BASE, C=13, zero_padded_shift=True, scaling=0.3), 22, (16, 16)),
+        "classic_c5_hd20_b2_11x13": (dict(BASE, C=5, Hd=20), 23, (11, 13)),
+    }
+
+
+def shape_class_cases():
+    """The padded-channel fixtures, on a generator of their own (the draws of the fixtures above do
+    not move when one is added here)."""
+    gen = torch.Generator().manual_seed(SHAPE_CLASS_SEED)
+    for name, (k, seed, (H, W)) in shape_class_knobs().items():
+        graph = name.startswith("graph")
+        m = make_graph(k, None, seed) if graph else make_classic(k, None, seed)
+        save_case(name, m, k, blob_state(2, k["C"], H, W, gen), 0.5, graph=graph,
+                  return_attention=graph and k["zero_padded_shift"])
 
 
 if __name__ == "__main__":
-    main()
+    shape_class_cases() if "--shape-classes" in sys.argv[1:] else main()

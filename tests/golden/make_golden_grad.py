@@ -3,6 +3,7 @@
 Run in the build container only (it needs /root/reference):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grad.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grad.py --shape-classes   # those three only
 
 Two kinds of fixture (data only; the reference source never leaves the container):
 
@@ -33,7 +34,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from make_golden import (BASE, CK_CLASSIC, CK_GRAPH, blob_state, grow, load_state,  # noqa: E402
-                         make_classic, make_graph, random_state)
+                         make_classic, make_graph, random_state, shape_class_knobs)
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -157,6 +158,16 @@ def save_bptt_case(name, model, knobs, x0, target, steps, frs, use_graph, gain, 
     print(f"bptt_{name}: {os.path.getsize(path)/1024:.0f} KB T={T} loss={float(loss):.6f}")
 
 
+def shape_class_cases():
+    """One-step gradients at channel counts that are no multiple of 4 (make_golden.shape_class_knobs),
+    on a generator of their own."""
+    gen = torch.Generator().manual_seed(4177)
+    for name, (k, seed, (H, W)) in shape_class_knobs().items():
+        graph = name.startswith("graph")
+        m = make_graph(k, None, seed) if graph else make_classic(k, None, seed)
+        save_grad_case(name, m, k, blob_state(2, k["C"], H, W, gen), 0.5, graph=graph)
+
+
 def main():
     gen = torch.Generator().manual_seed(777)
     latest = load_state(f"{CK_GRAPH}/nca_latest.pt")
@@ -219,7 +230,8 @@ def main():
     save_bptt_case("graph_zeropad_latest_b3_32_t6", make_graph(kz, latest), kz, x0, target, steps, frs, ug, 0.25)
     save_bptt_case("classic_ep980_b3_32_t6", make_classic(kc, classic), kc, x0, target, steps,
                    frs, ug, 0.0)
+    shape_class_cases()
 
 
 if __name__ == "__main__":
-    main()
+    shape_class_cases() if "--shape-classes" in sys.argv[1:] else main()

@@ -43,7 +43,8 @@ def test_vjp_matches_reference_f64(name):
     assert_grads_close(grads, c.grads(f64=True), 1e-10, c.meta["zero_padded_shift"])
 
 
-@pytest.mark.parametrize("name", grad_case_names()[:6])
+# (every fixture, not a slice of the sorted names: a new fixture must not push another one out)
+@pytest.mark.parametrize("name", grad_case_names())
 def test_vjp_forward_consistent(name):
     """The fixture's forward output matches the oracle forward (sanity of the recorded draws)."""
     c = Case(name)
