@@ -6,6 +6,8 @@ The HIP kernels live in csrc/ and are built into libgnca.so (C ABI: include/gnca
 from .damage import DamagePolicy, regrow_trace
 from .modules import FixedSobelPerception, GraphAugmentation, NeuralCA, NeuralCAGraph
 from .render import CMAPS, colorize, render_rgb
+from .vitals import StateVitals, state_vitals
 
 __all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph",
-           "render_rgb", "colorize", "CMAPS", "DamagePolicy", "regrow_trace"]
+           "render_rgb", "colorize", "CMAPS", "DamagePolicy", "regrow_trace",
+           "state_vitals", "StateVitals"]

@@ -91,6 +91,17 @@ class GraphDiagOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in DIAG_FIELDS]
 
 
+VITALS_FIELDS = ("alive", "mature", "alpha_sum", "mass", "cy", "cx", "y0", "y1", "x0", "x1", "max_abs",
+                 "nonfinite", "hidden_rms")
+VITALS_BAND_ROWS, VITALS_TILE_COLS = 8, 256   # the tile of one sample that one workgroup of gnca_state_vitals
+                                              # reads (include/gnca.h)
+
+
+class TraceVitals(ctypes.Structure):
+    """Mirror of gnca_trace_vitals (include/gnca.h): the threshold and the device output [R,B,13]."""
+    _fields_ = [("alpha_thr", ctypes.c_float), ("out", ctypes.c_void_p)]
+
+
 class DamageDesc(ctypes.Structure):
     """Mirror of gnca_damage_desc (include/gnca.h)."""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -186,7 +197,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_loss_masked_f32", "gnca_loss_masked_bwd_f32", "gnca_loss_stability_workspace_bytes",
            "gnca_loss_stability_f32", "gnca_loss_stability_bwd_f32", "gnca_optim_step", "gnca_pool_commit",
            "gnca_graph_diag_workspace_bytes", "gnca_graph_diag", "gnca_rollout_trace_diag_workspace_bytes",
-           "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy")
+           "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy",
+           "gnca_state_vitals_workspace_bytes", "gnca_state_vitals",
+           "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -333,6 +346,20 @@ def load(path: str = LIB_PATH):
         if hasattr(lib, "gnca_damage_policy"):   # (likewise)
             lib.gnca_damage_policy.restype = ctypes.c_int
             lib.gnca_damage_policy.argtypes = [ctypes.POINTER(DamagePolicyDesc), vp, vp, vp, vp, vp]
+        if hasattr(lib, "gnca_state_vitals"):   # (likewise)
+            do = ctypes.POINTER(GraphDiagOut)
+            lib.gnca_state_vitals_workspace_bytes.restype = sz
+            lib.gnca_state_vitals_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            lib.gnca_state_vitals.restype = ctypes.c_int
+            lib.gnca_state_vitals.argtypes = [i32, i32, i32, i32, vp, i64, ctypes.c_float, vp, vp, sz, vp]
+            lib.gnca_rollout_trace_vitals_workspace_bytes.restype = sz
+            lib.gnca_rollout_trace_vitals_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc),
+                                                                      ctypes.POINTER(TraceArgs),
+                                                                      ctypes.POINTER(TraceMetrics), do]
+            lib.gnca_rollout_trace_vitals.restype = ctypes.c_int
+            lib.gnca_rollout_trace_vitals.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                      ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics), do,
+                                                      ctypes.POINTER(TraceVitals), vp, vp, vp, sz, vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

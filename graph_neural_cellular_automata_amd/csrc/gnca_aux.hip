@@ -744,6 +744,203 @@ int met_bands(int32_t N, int32_t H) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// State vitals (include/gnca.h, gnca_state_vitals): how much of a state is alive, where its pattern
+// lies and whether it is still finite, for the whole batch in one pass over the state.
+//
+// One workgroup per (sample, band of kVitBand rows, chunk of kVitCols columns).  The tile's alpha
+// cells and a one-cell halo around them are staged in LDS (cells outside the image as -inf: they
+// never pass a threshold), so the 3x3 pool, the counts, the sums, the centroid and the bounding box
+// come from LDS; the other C - 1 planes are read once each with kVitU loads per thread in flight
+// (V = 4 where W % 4 == 0: four cells per thread, one 16-byte load where the addresses allow it, else
+// four 4-byte loads of the same cells, so the order of every sum depends on the shape alone) and feed
+// max_abs, nonfinite and the hidden sum of squares.  Every sum is fp64 (counts as fp64 integers) in an order fixed by (C, H, W): per thread, xor-shuffle, the
+// waves in order, then the tiles' partials by one wave per sample (lane l adds tiles l, l + 64, ...,
+// then the same butterfly).  A sample's 13 numbers are therefore bitwise the same in any batch.
+// ---------------------------------------------------------------------------------------------
+constexpr int kVitBand = GNCA_VITALS_BAND_ROWS;   // rows per workgroup
+constexpr int kVitCols = GNCA_VITALS_TILE_COLS;   // columns per workgroup (10 KB LDS)
+static_assert(kVitCols % 4 == 0, "a tile starts on a 16-byte column where W % 4 == 0");
+constexpr int kVitU = 5;                          // planes a thread has in flight
+constexpr int kVitF = GNCA_VITALS_FIELDS;
+constexpr double kVitNoCell = 2147483647.0;       // y0 / x0 of a tile without a mature cell
+
+// Partials, one kVitF-vector per tile: the output fields' order, with Σ clip·i and Σ clip·j in place
+// of the centroid and Σ v² in place of the rms.  Fields 6 and 8 combine by min, 7, 9 and 10 by max,
+// the others by addition.
+__device__ __forceinline__ double vit_combine(int f, double a, double b) {
+  if (f == 6 || f == 8) return fmin(a, b);
+  if (f == 7 || f == 9 || f == 10) return fmax(a, b);
+  return a + b;
+}
+
+__device__ __forceinline__ double vit_identity(int f) {
+  if (f == 6 || f == 8) return kVitNoCell;
+  if (f == 7 || f == 9) return -1.0;
+  return 0.0;
+}
+
+// every lane of the wave calls it: all lanes end with the wave's combined partials
+__device__ __forceinline__ void vit_wave_reduce(double s[kVitF]) {
+#pragma unroll
+  for (int f = 0; f < kVitF; ++f)
+    for (int off = 32; off > 0; off >>= 1) s[f] = vit_combine(f, s[f], __shfl_xor(s[f], off));
+}
+
+// one value of any plane: the largest finite magnitude, the non-finite count and (hidden planes)
+// the finite values' sum of squares
+__device__ __forceinline__ void vit_value(float v, bool hidden, float& mx, int& nf, double& hs) {
+  const float av = fabsf(v);
+  const bool fin = av <= 3.402823466e+38f;   // false for NaN and +-inf
+  mx = fmaxf(mx, fin ? av : 0.f);
+  nf += fin ? 0 : 1;
+  if (hidden) {   // (uniform over the workgroup)
+    const double d = fin ? (double)v : 0.0;
+    hs = fma(d, d, hs);
+  }
+}
+
+template <int V, bool A>
+__global__ __launch_bounds__(kThreads) void gnca_state_vitals_k(int C, int H, int W, int nbands, int nchunks,
+                                                                const float* x, long xbs, float thr,
+                                                                double* part) {
+  typedef float vf __attribute__((ext_vector_type(V)));
+  __shared__ float as[kVitBand + 2][kVitCols + 2];
+  __shared__ double red[kThreads / 64][kVitF];
+  const int tid = threadIdx.x;
+  const int chunk = (int)(blockIdx.x % (unsigned)nchunks);
+  const int sb = (int)(blockIdx.x / (unsigned)nchunks);
+  const int band = sb % nbands, b = sb / nbands;
+  const size_t HW = (size_t)H * W;
+  const float* xb = x + (size_t)b * xbs;
+  const int r0 = band * kVitBand, nr = min(kVitBand, H - r0);   // 1 .. kVitBand rows
+  const int c0 = chunk * kVitCols, nc = min(kVitCols, W - c0);  // 1 .. kVitCols columns
+  float mx = 0.f;
+  int nf = 0;
+  double hs = 0.0;
+
+  // the alpha tile and its halo: as[tr][tc] = alpha(r0 - 1 + tr, c0 - 1 + tc)
+  const float* ap = xb + 3 * HW;
+  const int tw = nc + 2;
+  for (int e = tid; e < (nr + 2) * tw; e += kThreads) {
+    const int tr = e / tw, tc = e - tr * tw;
+    const int i = r0 - 1 + tr, j = c0 - 1 + tc;
+    float a = -INFINITY;
+    if (i >= 0 && i < H && j >= 0 && j < W) {
+      a = ap[(size_t)i * W + j];
+      if (tr >= 1 && tr <= nr && tc >= 1 && tc <= nc) vit_value(a, false, mx, nf, hs);   // the tile's own cells
+    }
+    as[tr][tc] = a;
+  }
+
+  // the other planes: q = 0..2 are the colours, q >= 3 the hidden channels q + 1
+  const int nvc = nc / V;   // (V = 4 only where W % 4 == 0, and kVitCols % 4 == 0)
+  for (int e = tid; e < nr * nvc; e += kThreads) {
+    const int r = e / nvc, v = e - r * nvc;
+    const float* p = xb + (size_t)(r0 + r) * W + (size_t)(c0 + V * v);
+    for (int q0 = 0; q0 < C - 1; q0 += kVitU) {
+      vf val[kVitU];
+#pragma unroll
+      for (int u = 0; u < kVitU; ++u) {
+        const int q = q0 + u;
+        if (q < C - 1) {
+          const float* pq = p + (size_t)(q < 3 ? q : q + 1) * HW;
+          if constexpr (A) {
+            val[u] = *reinterpret_cast<const vf*>(pq);
+          } else {
+#pragma unroll
+            for (int l = 0; l < V; ++l) val[u][l] = pq[l];
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kVitU; ++u) {
+        const int q = q0 + u;
+        if (q < C - 1) {
+#pragma unroll
+          for (int l = 0; l < V; ++l) vit_value(val[u][l], q >= 3, mx, nf, hs);
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  int alive = 0, mature = 0, y0 = 0x7fffffff, y1 = -1, x0 = 0x7fffffff, x1 = -1;
+  double asum = 0.0, mass = 0.0, sy = 0.0, sx = 0.0;
+  for (int e = tid; e < nr * nc; e += kThreads) {
+    const int r = e / nc, c = e - r * nc;
+    float m = -INFINITY;   // the 3x3 pool around as[r + 1][c + 1]
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) m = fmaxf(m, as[r + dy][c + dx]);
+    const float a = as[r + 1][c + 1];
+    const int i = r0 + r, j = c0 + c;
+    alive += m > thr ? 1 : 0;
+    if (a > thr) {
+      ++mature;
+      y0 = min(y0, i); y1 = max(y1, i); x0 = min(x0, j); x1 = max(x1, j);
+    }
+    const double cl = (double)fminf(fmaxf(a, 0.f), 1.f);
+    asum += (double)a;
+    mass += cl;
+    sy = fma(cl, (double)i, sy);   // (the products are exact)
+    sx = fma(cl, (double)j, sx);
+  }
+
+  double s[kVitF] = {(double)alive, (double)mature, asum, mass, sy, sx, (double)y0, (double)y1,
+                     (double)x0,    (double)x1,     (double)mx, (double)nf, hs};
+  vit_wave_reduce(s);
+  if ((tid & 63) == 0)
+#pragma unroll
+    for (int f = 0; f < kVitF; ++f) red[tid >> 6][f] = s[f];
+  __syncthreads();
+  if (tid < kVitF) {
+    double v = red[0][tid];
+    for (int w = 1; w < kThreads / 64; ++w) v = vit_combine(tid, v, red[w][tid]);
+    part[(size_t)blockIdx.x * kVitF + tid] = v;
+  }
+}
+
+// one wave per sample: its tiles' partials combined in a fixed order, then the 13 fields
+__global__ __launch_bounds__(kThreads) void gnca_state_vitals_finish(int B, int C, int H, int W, int np,
+                                                                     const double* part, double* out) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (b >= B) return;   // (uniform over the wave)
+  double s[kVitF];
+#pragma unroll
+  for (int f = 0; f < kVitF; ++f) s[f] = vit_identity(f);
+  for (int p = lane; p < np; p += 64) {
+    const double* q = part + ((size_t)b * np + p) * kVitF;
+#pragma unroll
+    for (int f = 0; f < kVitF; ++f) s[f] = vit_combine(f, s[f], q[f]);
+  }
+  vit_wave_reduce(s);
+  if (lane != 0) return;
+  double* o = out + (size_t)b * kVitF;
+  const bool none = s[1] == 0.0;
+  o[0] = s[0];
+  o[1] = s[1];
+  o[2] = s[2];
+  o[3] = s[3];
+  o[4] = s[4] / s[3];   // (0 / 0: NaN)
+  o[5] = s[5] / s[3];
+#pragma unroll
+  for (int f = 6; f < 10; ++f) o[f] = none ? -1.0 : s[f];
+  o[10] = s[10];
+  o[11] = s[11];
+  o[12] = C > 4 ? sqrt(s[12] / ((double)(C - 4) * (double)H * (double)W)) : 0.0;
+}
+
+// tiles per sample: a function of (H, W) alone (0: too many workgroups for one launch)
+long vit_tiles(int32_t B, int32_t H, int32_t W, int* nbands, int* nchunks) {
+  *nbands = (H + kVitBand - 1) / kVitBand;
+  *nchunks = (W + kVitCols - 1) / kVitCols;
+  const long np = (long)*nbands * *nchunks;
+  return np * (long)B > 0x7fffffffL ? 0 : np;
+}
+
+// ---------------------------------------------------------------------------------------------
 // The iteration's tail (train_graph_augmented_nca.py:367-391, train_intermediate_loss.py:269-296):
 // gradient policy + Adam over a by-value table of tensors, and the pool write-back.  Both move a few
 // tens of KB: what counts is one launch, no host wait and a fixed summation order.
@@ -1138,6 +1335,42 @@ extern "C" int gnca_image_metrics_f32(int32_t N, int32_t H, int32_t W, const flo
   if (e == hipSuccess && nb > 1) {
     hipLaunchKernelGGL(gnca_image_metrics_finish, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        st, N, nb, H, W, part, out);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+extern "C" size_t gnca_state_vitals_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+  if (B <= 0 || C < 4 || H <= 0 || W <= 0) return 0;
+  int nbands, nchunks;
+  return (size_t)B * (size_t)vit_tiles(B, H, W, &nbands, &nchunks) * kVitF * sizeof(double);
+}
+
+extern "C" int gnca_state_vitals(int32_t B, int32_t C, int32_t H, int32_t W, const float* x, int64_t x_bstride,
+                                 float alpha_thr, double* out, void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0 || C < 4 || H <= 0 || W <= 0 || !x || !out || x_bstride < 0 || ((uintptr_t)out & 7))
+    return GNCA_ERR_INVALID;
+  int nbands, nchunks;
+  const long np = vit_tiles(B, H, W, &nbands, &nchunks);
+  if (np == 0) return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < (size_t)B * (size_t)np * kVitF * sizeof(double) || ((uintptr_t)ws & 7))
+    return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(ws);
+  const dim3 grid((unsigned)(np * B));
+  // four cells per thread where W % 4 == 0 (a function of the shape: the sums' order), as one 16-byte
+  // load where every address is 16-byte aligned
+  const bool aligned = x_bstride % 4 == 0 && ((uintptr_t)x & 15) == 0;
+  auto kern = W % 4 != 0 ? gnca_state_vitals_k<1, true>
+                         : (aligned ? gnca_state_vitals_k<4, true> : gnca_state_vitals_k<4, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, st, C, H, W, nbands, nchunks, x, (long)x_bstride, alpha_thr,
+                     part);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    constexpr int per = kThreads / 64;   // samples per finish workgroup
+    hipLaunchKernelGGL(gnca_state_vitals_finish, dim3((unsigned)((B + per - 1) / per)), dim3(kThreads), 0, st, B, C,
+                       H, W, (int)np, part, out);
     e = hipGetLastError();
   }
   if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }

@@ -3326,13 +3326,13 @@ static int frame_copy(const float* src, float* dst, int B, int fc, int C, size_t
 }
 
 // [state A | state B | scratch | rollout workspace | attention workspace | metrics workspace |
-//  diagnostics workspace]
+//  diagnostics workspace | vitals workspace]
 struct TraceLayout {
-  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, off_met, met_ws, off_diag, diag_ws, bytes;
+  size_t state, off_scratch, off_ws, ws, off_attn, attn_ws, off_met, met_ws, off_diag, diag_ws, off_vit, vit_ws, bytes;
 };
 
 static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, const gnca_trace_metrics* m,
-                         TraceLayout* L, bool diag = false) {
+                         TraceLayout* L, bool diag = false, bool vitals = false) {
   if (!d || !a || a->steps < 0 || a->num_records < 0 || a->flags != 0) return false;
   if (a->num_records > 0 && !a->record) return false;
   for (int r = 0; r < a->num_records; ++r) {
@@ -3373,7 +3373,14 @@ static bool trace_layout(const gnca_step_desc* d, const gnca_trace_args* a, cons
     if (!diag_layout(&dt, &D)) return false;
     L->diag_ws = D.bytes;
   }
-  L->bytes = L->off_diag + L->diag_ws;
+  L->off_vit = L->off_diag + L->diag_ws;
+  L->vit_ws = 0;
+  if (vitals) {   // (the pieces before it keep their places: the call without vitals lays out the same)
+    L->off_vit = align256(L->off_vit);
+    L->vit_ws = gnca_state_vitals_workspace_bytes(d->B, d->C, d->H, d->W);
+    if (L->vit_ws == 0) return false;
+  }
+  L->bytes = L->off_vit + L->vit_ws;
   return true;
 }
 
@@ -3392,16 +3399,19 @@ static gnca_graph_diag_out diag_record(const gnca_graph_diag_out& o, size_t r, s
   return q;
 }
 
-// gnca_rollout_trace_f32 (m == nullptr) / gnca_rollout_trace_metrics_f32 / gnca_rollout_trace_diag (diag set)
+// gnca_rollout_trace_f32 (m == nullptr) / gnca_rollout_trace_metrics_f32 / gnca_rollout_trace_diag (diag set) /
+// gnca_rollout_trace_vitals (vit set)
 static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
                       const gnca_trace_metrics* m, const float* x, float* x_final, void* ws, size_t ws_bytes,
-                      void* stream, const gnca_graph_diag_out* diag = nullptr) {
+                      void* stream, const gnca_graph_diag_out* diag = nullptr,
+                      const gnca_trace_vitals* vit = nullptr) {
   if (!desc || !w || !args || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
   TraceLayout L;
-  if (!trace_layout(desc, args, m, &L, diag != nullptr))
+  if (!trace_layout(desc, args, m, &L, diag != nullptr, vit != nullptr))
     return (diag && desc->C > 32) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
   const int T = args->steps, R = args->num_records, fc = args->frame_channels;
-  if (R > 0 && !args->frames && !m && !diag) return GNCA_ERR_INVALID;
+  if (R > 0 && !args->frames && !m && !diag && !vit) return GNCA_ERR_INVALID;
+  if (vit && R > 0 && !vit->out) return GNCA_ERR_INVALID;
   // (target and out both NULL: nothing is measured, a trace that may go without frames)
   if (m && (m->target_bstride < 0 || (m->target == nullptr) != (m->out == nullptr))) return GNCA_ERR_INVALID;
   const bool measure = m && m->out;
@@ -3457,6 +3467,11 @@ static int trace_impl(const gnca_step_desc* desc, const gnca_weights* w, const g
       if (measure && (rc = gnca_image_metrics_f32(desc->B, desc->H, desc->W, dst, (int64_t)desc->C * (int64_t)HW,
                                             m->target, m->target_bstride, m->out + (size_t)r * desc->B * 4,
                                             wsb + L.off_met, L.met_ws, stream)) != GNCA_OK)
+        return rc;
+      // the vitals read all C channels of the same state in place
+      if (vit && (rc = gnca_state_vitals(desc->B, desc->C, desc->H, desc->W, dst, (int64_t)desc->C * (int64_t)HW,
+                                         vit->alpha_thr, vit->out + (size_t)r * desc->B * GNCA_VITALS_FIELDS,
+                                         wsb + L.off_vit, L.vit_ws, stream)) != GNCA_OK)
         return rc;
       ++r;
     }
@@ -3529,6 +3544,20 @@ int gnca_rollout_trace_diag(const gnca_step_desc* desc, const gnca_weights* w, c
                             float* x_final, void* ws, size_t ws_bytes, void* stream) {
   if (!diag) return GNCA_ERR_INVALID;
   return trace_impl(desc, w, args, m, x, x_final, ws, ws_bytes, stream, diag);
+}
+
+size_t gnca_rollout_trace_vitals_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                                 const gnca_trace_metrics* m, const gnca_graph_diag_out* diag) {
+  TraceLayout L;
+  return trace_layout(desc, args, m, &L, diag != nullptr, true) ? L.bytes : 0;
+}
+
+int gnca_rollout_trace_vitals(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                              const gnca_trace_metrics* m, const gnca_graph_diag_out* diag,
+                              const gnca_trace_vitals* vitals, const float* x, float* x_final, void* ws,
+                              size_t ws_bytes, void* stream) {
+  if (!vitals) return GNCA_ERR_INVALID;
+  return trace_impl(desc, w, args, m, x, x_final, ws, ws_bytes, stream, diag, vitals);
 }
 
 }  // extern "C"

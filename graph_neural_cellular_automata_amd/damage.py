@@ -334,6 +334,7 @@ def regrow_trace(model, x, steps: int, policy: DamagePolicy, damage_step: int, *
     from .metrics import ImageMetrics
     from .modules._stepper import TraceResult
     from .step import GraphDiagnostics
+    from .vitals import StateVitals
     for name, v in (("steps", steps), ("damage_step", damage_step)):
         if isinstance(v, bool) or not isinstance(v, int) or v < 0:
             raise ValueError(f"{name} must be a non-negative int, got {v!r}")
@@ -374,6 +375,7 @@ def regrow_trace(model, x, steps: int, policy: DamagePolicy, damage_step: int, *
         da, db = a.diagnostics, b.diagnostics
         diag = GraphDiagnostics(offsets=list(da.offsets or []) + list(db.offsets or []),
                                 **{n: _cat([getattr(da, n), getattr(db, n)]) for n in L.DIAG_FIELDS})
+    vitals = None if b.vitals is None else StateVitals(torch.cat([a.vitals.stacked, b.vitals.stacked], 0))
     return TraceResult(b.x_final, _cat([a.frames, b.frames]), rec1 + [r + damage_step for r in rec2],
                        _cat([a.attention, b.attention]), metrics, diag, rgb_u8=_cat([a.rgb_u8, b.rgb_u8]),
-                       attention_u8=_cat([a.attention_u8, b.attention_u8]))
+                       attention_u8=_cat([a.attention_u8, b.attention_u8]), vitals=vitals)

@@ -10,6 +10,7 @@ from .. import _lib as L
 from .. import metrics as M
 from .. import render as R
 from .. import step as S
+from .. import vitals as V
 
 
 class _ParamPack(torch.autograd.Function):
@@ -365,16 +366,19 @@ class TraceResult:
     with the R axis (each recorded step's input state with that step's offsets) or None.  With
     ``render``: ``rgb_u8`` uint8 [R,B,H*s,W*s,3|4], the frames as images (``render.render_rgb``), and
     ``attention_u8`` uint8 [R,B,H,W,3], the attention maps as colour images (``render.colorize``), or
-    None.  All detached."""
+    None.  ``vitals``: a ``StateVitals`` of shape [R,B] (``vitals.state_vitals`` of the whole state after
+    each recorded step) or None.  All detached."""
 
-    __slots__ = ("x_final", "frames", "steps", "attention", "metrics", "rgb_u8", "attention_u8", "diagnostics")
+    __slots__ = ("x_final", "frames", "steps", "attention", "metrics", "rgb_u8", "attention_u8", "vitals",
+                 "diagnostics")
 
     def __init__(self, x_final, frames, steps, attention, metrics=None, diagnostics=None, *, rgb_u8=None,
-                 attention_u8=None):
+                 attention_u8=None, vitals=None):
         self.x_final, self.frames, self.steps, self.attention = x_final, frames, steps, attention
         self.metrics = metrics
         self.diagnostics = diagnostics
         self.rgb_u8, self.attention_u8 = rgb_u8, attention_u8
+        self.vitals = vitals
 
     def __repr__(self):
         shape = lambda t: None if t is None else tuple(t.shape)
@@ -383,13 +387,14 @@ class TraceResult:
                 f"metrics={None if self.metrics is None else shape(self.metrics.stacked)}"
                 + ("" if self.rgb_u8 is None else f", rgb_u8={shape(self.rgb_u8)}")
                 + ("" if self.attention_u8 is None else f", attention_u8={shape(self.attention_u8)}")
-                + ("" if self.diagnostics is None else ", diagnostics") + ")")
+                + ("" if self.diagnostics is None else ", diagnostics")
+                + ("" if self.vitals is None else f", vitals={shape(self.vitals.stacked)}") + ")")
 
 
 def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, every=1, record=None,
               channels=4, return_attention=False, fire_rate=1.0, message_gain=None, seed=None, sample_base=0,
               first_step=0, offsets=None, target=None, frames=True, diagnostics=False,
-              per_offset=False, render=None) -> TraceResult:
+              per_offset=False, render=None, vitals=False) -> TraceResult:
     """The shared body of ``NeuralCA.trace`` / ``NeuralCAGraph.trace``: a no-grad rollout that records
     frames (and attention maps, image metrics against ``target`` and graph diagnostics) in one native
     call; ``render`` adds one launch over all recorded frames and one over all attention maps."""
@@ -407,6 +412,11 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
         raise ValueError("per_offset is part of the diagnostics: pass diagnostics=True")
     if target is not None:
         target = M.check_target(target, B, H, W)
+    vitals_thr = None   # vitals: False, True (the model's alpha_thr) or the threshold itself
+    if vitals is True:
+        vitals_thr = V.check_alpha_thr(model.alpha_thr, "the model's alpha_thr")
+    elif vitals is not False:
+        vitals_thr = V.check_alpha_thr(vitals, "vitals (a bool, or the alpha threshold)")
     render = R.check_trace_render(render, model.alpha_thr, channels, frames)
     # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
     plan = S.build_trace(steps=steps, B=B, C=C, H=H, W=W, device=x.device, every=every, record=record,
@@ -418,8 +428,16 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
         sched = plan.schedule
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
         desc.rng_step = plan.first_step
-        met = diag = None
-        if diagnostics:
+        met = diag = vit = None
+        if vitals_thr is not None:
+            tgt, tbs = (None, 0) if target is None else M.device_target(target, x.device)
+            out, frm, attn, met, diag, vit = S.trace_vitals(desc, w, x, steps, sched.offsets or [], plan.record,
+                                                            plan.channels, vitals_thr, tgt, tbs,
+                                                            want_attention=plan.attention, want_frames=frames,
+                                                            diagnostics=diagnostics, per_offset=per_offset)
+            met = None if met is None else M.ImageMetrics(met)
+            vit = V.StateVitals(vit)
+        elif diagnostics:
             tgt, tbs = (None, 0) if target is None else M.device_target(target, x.device)
             out, frm, attn, met, diag = S.trace_diag(desc, w, x, steps, sched.offsets or [], plan.record,
                                                      plan.channels, tgt, tbs, want_attention=plan.attention,
@@ -440,4 +458,5 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
             rgb_u8 = R.render_rgb(frm, render["alpha_thr"], render["upscale"], render["mode"])
             if attn is not None:
                 attn_u8 = R.colorize(attn, render["cmap"])
-    return TraceResult(out, frm, list(plan.record), attn, met, diag, rgb_u8=rgb_u8, attention_u8=attn_u8)
+    return TraceResult(out, frm, list(plan.record), attn, met, diag, rgb_u8=rgb_u8, attention_u8=attn_u8,
+                       vitals=vit)

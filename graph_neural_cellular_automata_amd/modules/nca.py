@@ -47,7 +47,7 @@ class NeuralCA(nn.Module):
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
               sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
               frames: bool = True, diagnostics: bool = False, per_offset: bool = False,
-              render=None) -> TraceResult:
+              render=None, vitals=False) -> TraceResult:
         """``steps`` CA steps in one native call that also records frames: see ``NeuralCAGraph.trace``
         (same arguments and result; always under ``no_grad``, detached tensors).  The classic model
         has no graph term: ``return_attention=True``, ``diagnostics=True``, a ``message_gain`` or
@@ -60,4 +60,4 @@ class NeuralCA(nn.Module):
             raise ValueError("message_gain given for a model without the graph term")
         return run_trace(self, x, steps, None, False, every=every, record=record, channels=channels,
                          fire_rate=fire_rate, seed=seed, sample_base=sample_base, first_step=first_step,
-                         offsets=offsets, target=target, frames=frames, render=render)
+                         offsets=offsets, target=target, frames=frames, render=render, vitals=vitals)

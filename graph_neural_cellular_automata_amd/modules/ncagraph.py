@@ -99,7 +99,7 @@ class NeuralCAGraph(nn.Module):
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,
               sample_base: int = 0, first_step: int = 0, offsets=None, target=None,
               frames: bool = True, diagnostics: bool = False, per_offset: bool = False,
-              render=None) -> TraceResult:
+              render=None, vitals=False) -> TraceResult:
         """``steps`` CA steps in one native call that also records (extension, not in the reference):
         the per-step Python loop of the regeneration diagnostic and the video generators, on the
         rollout pipeline.  Always runs under ``no_grad`` and returns detached tensors, whatever the
@@ -138,9 +138,17 @@ class NeuralCAGraph(nn.Module):
         ``rgb_u8`` [R,B,H*upscale,W*upscale,3|4] is bitwise ``render.render_rgb(frames, ...)``
         (``alpha_thr=None``: ``self.alpha_thr``), and with ``return_attention`` its ``attention_u8``
         [R,B,H,W,3] is bitwise ``render.colorize(attention, cmap)``.  Needs ``frames=True`` and
-        ``channels >= 4``."""
+        ``channels >= 4``.
+
+        ``vitals=True`` (``alpha_thr = self.alpha_thr``) or ``vitals=<threshold>`` also takes
+        ``vitals.state_vitals`` of the whole state after each recorded step: the result's ``vitals`` is a
+        ``StateVitals`` of shape [R,B] (live and mature counts, alpha sums, centroid, bounding box, largest
+        magnitude, non-finite count, hidden rms), bitwise the standalone call on those states.  It works
+        with ``frames=False``: ``trace(x, T, every=1, frames=False, vitals=True).vitals.alive`` is a growth
+        curve.  The other results are bitwise those of the trace without it."""
         return run_trace(self, x, steps, self.graph, self.hidden_only, every=every, record=record,
                          channels=channels, return_attention=return_attention, fire_rate=fire_rate,
                          message_gain=self.message_gain if message_gain is None else message_gain, seed=seed,
                          sample_base=sample_base, first_step=first_step, offsets=offsets, target=target,
-                         frames=frames, diagnostics=diagnostics, per_offset=per_offset, render=render)
+                         frames=frames, diagnostics=diagnostics, per_offset=per_offset, render=render,
+                         vitals=vitals)

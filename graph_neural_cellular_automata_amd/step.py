@@ -590,15 +590,29 @@ def trace_diag(desc, weights, x, steps: int, offsets_per_step: list, record: lis
     Returns ``(x_final, frames or None, attention or None, metrics [R,B,4] or None, GraphDiagnostics
     with [R,...]-leading fields)``."""
     return _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
-                           want_attention, want_frames, bool(per_offset))
+                           want_attention, want_frames, bool(per_offset))[:5]
+
+
+def trace_vitals(desc, weights, x, steps: int, offsets_per_step: list, record: list, channels: int,
+                 alpha_thr: float, target=None, target_bstride: int = 0, want_attention: bool = False,
+                 want_frames: bool = True, diagnostics: bool = False, per_offset: bool = False):
+    """``trace_metrics`` / ``trace_diag`` that also takes the vitals of the state after each recorded
+    step (gnca_rollout_trace_vitals; ``vitals.state_vitals`` of all C channels, against ``alpha_thr``).
+    Returns ``(x_final, frames or None, attention or None, metrics [R,B,4] or None, GraphDiagnostics or
+    None, vitals [R,B,13] float64)``."""
+    return _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
+                           want_attention, want_frames, bool(per_offset) if diagnostics else None,
+                           vitals_thr=float(alpha_thr))
 
 
 def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels, target, target_bstride,
-                    want_attention, want_frames, diag_taps):
-    """The shared body of ``trace_metrics`` (``diag_taps`` None) and ``trace_diag`` (``diag_taps``: whether
-    the per-offset stack is recorded too)."""
+                    want_attention, want_frames, diag_taps, vitals_thr=None):
+    """The shared body of ``trace_metrics`` (``diag_taps`` None), ``trace_diag`` (``diag_taps``: whether
+    the per-offset stack is recorded too) and ``trace_vitals`` (``vitals_thr`` set, beside either)."""
     lib = L.load()
     fn = _diag_entry("gnca_rollout_trace_diag") if diag_taps is not None else None
+    if vitals_thr is not None:
+        fn = _diag_entry("gnca_rollout_trace_vitals")
     k = desc.num_offsets
     flat = [v for offs in offsets_per_step for o in offs for v in o]
     if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
@@ -623,25 +637,45 @@ def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels,
         # (R = 0: a placeholder element keeps both pointers set; nothing is written)
         keep_out = met if R else torch.empty(4, dtype=torch.float32, device=x.device)
         m.target, m.target_bstride, m.out = target.data_ptr(), int(target_bstride), keep_out.data_ptr()
-    size = lib.gnca_rollout_trace_metrics_workspace_bytes if fn is None else lib.gnca_rollout_trace_diag_workspace_bytes
-    n = size(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
+    if vitals_thr is not None:
+        t, o = _diag_buffers(desc, x.device, diag_taps, lead=(R,)) if diag_taps is not None else (None, None)
+        op = None if o is None else ctypes.byref(o)
+        n = lib.gnca_rollout_trace_vitals_workspace_bytes(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m), op)
+    else:
+        size = (lib.gnca_rollout_trace_metrics_workspace_bytes if fn is None
+                else lib.gnca_rollout_trace_diag_workspace_bytes)
+        n = size(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
     if n == 0:
         raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
                           f"hidden={desc.hidden} ({SUPPORT_SET})")
     ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    if vitals_thr is not None:
+        vit = torch.empty(R, desc.B, len(L.VITALS_FIELDS), dtype=torch.float64, device=x.device)
+        v = L.TraceVitals()
+        v.alpha_thr, v.out = float(vitals_thr), (vit.data_ptr() if R else None)
+        rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), ctypes.byref(m), op, ctypes.byref(v),
+                x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+        L.check(rc, "gnca_rollout_trace_vitals")
+        diag = None if t is None else _trace_diagnostics(desc, offsets_per_step, record, t)
+        return out, frames, attn, met, diag, vit
     if fn is None:
         rc = lib.gnca_rollout_trace_metrics_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a),
                                                 ctypes.byref(m), x.data_ptr(), out.data_ptr(), ws.data_ptr(),
                                                 ws.numel(), stream_ptr(x.device))
         L.check(rc, "gnca_rollout_trace_metrics_f32")
-        return out, frames, attn, met, None
+        return out, frames, attn, met, None, None
     t, o = _diag_buffers(desc, x.device, diag_taps, lead=(R,))
     rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), ctypes.byref(m), ctypes.byref(o),
             x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
     L.check(rc, "gnca_rollout_trace_diag")
-    has = (desc.flags & L.GRAPH) and k > 0
+    return out, frames, attn, met, _trace_diagnostics(desc, offsets_per_step, record, t), None
+
+
+def _trace_diagnostics(desc, offsets_per_step, record, fields):
+    """A trace's ``GraphDiagnostics``: the recorded steps' offsets beside the [R,...]-leading fields."""
+    has = (desc.flags & L.GRAPH) and desc.num_offsets > 0
     offs = [[tuple(p) for p in offsets_per_step[r - 1]] if has else [] for r in record]
-    return out, frames, attn, met, GraphDiagnostics(offs, **t)
+    return GraphDiagnostics(offs, **fields)
 
 
 class GraphDiagnostics:

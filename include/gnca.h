@@ -528,6 +528,61 @@ int gnca_rollout_trace_diag(const gnca_step_desc* desc, const gnca_weights* w, c
                             float* x_final, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * State vitals: how much of a state is alive, where its pattern lies and whether it is still
+ * finite, as device numbers, and a recording rollout that takes them.  Neither name carries the
+ * _f32 suffix.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_VITALS_FIELDS 13
+#define GNCA_VITALS_BAND_ROWS 8    /* one workgroup reads a tile of 8 rows ...              */
+#define GNCA_VITALS_TILE_COLS 256  /* ... by 256 columns of one sample, all C channels      */
+
+/*
+ * x: [B,C,H,W] fp32, C >= 4, channel stride H*W, sample stride x_bstride floats.  out[b*13 + f], fp64,
+ * with a = channel 3 and every comparison in fp32 against alpha_thr as given:
+ *    0  alive       cells with max_pool3x3(a) > alpha_thr (neighbours outside the image do not count):
+ *                   the model's alive mask
+ *    1  mature      cells with a > alpha_thr
+ *    2  alpha_sum   sum of a
+ *    3  mass        sum of clip(a, 0, 1)
+ *  4,5  cy, cx      sum of clip(a,0,1) * i / mass, sum of clip(a,0,1) * j / mass; NaN when mass = 0
+ * 6..9  y0,y1,x0,x1 inclusive bounding box of the mature cells; all -1 when there is none
+ *   10  max_abs     largest |v| over all C channels and cells among finite v; 0 when there is none
+ *   11  nonfinite   number of NaN / +-inf values over all C channels
+ *   12  hidden_rms  sqrt(sum of v^2 / ((C-4) H W)) over the channels >= 4, finite v only; 0 when C = 4
+ * Fields 0..9 are specified only for a finite alpha plane; 10 and 11 always.  One pass over the state.
+ * Every sum is fp64 in a fixed order, without atomics: a sample's 13 numbers are bitwise the same
+ * whatever B is and wherever the sample stands in the batch.  Two launches on `hip_stream` (a
+ * hipStream_t, as the `stream` of the entry points above; DESIGN.md section 18 on the name), no allocation,
+ * no host synchronisation, capturable.  ws: >= gnca_state_vitals_workspace_bytes(B, C, H, W) bytes of
+ * device memory, 8-B aligned (else GNCA_ERR_WORKSPACE); the size is 0 on an invalid shape.  out: 8-B
+ * aligned.  B, C, H, W <= 0, C < 4, a null x / out or a negative stride: GNCA_ERR_INVALID.
+ */
+size_t gnca_state_vitals_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int gnca_state_vitals(int32_t B, int32_t C, int32_t H, int32_t W, const float* x, int64_t x_bstride,
+                      float alpha_thr, double* out, void* ws, size_t ws_bytes, void* hip_stream);
+
+typedef struct gnca_trace_vitals {
+  float alpha_thr;
+  double* out;              /* DEVICE [R,B,13]: the vitals of the state after step record[r]       */
+} gnca_trace_vitals;
+
+/*
+ * gnca_rollout_trace_diag that also takes the vitals: the same pieces and launches, and at each
+ * record point gnca_state_vitals of the piece's output state (all C channels, read in place) goes to
+ * vitals->out[r].  metrics and diag may each be NULL; args->frames may be NULL.  The frames, maps,
+ * metrics, diagnostics and x_final are bitwise those of the call without vitals, and the vitals those
+ * of gnca_state_vitals on the recorded states.  vitals NULL, or vitals->out NULL with num_records > 0:
+ * GNCA_ERR_INVALID.
+ */
+size_t gnca_rollout_trace_vitals_workspace_bytes(const gnca_step_desc* desc, const gnca_trace_args* args,
+                                                 const gnca_trace_metrics* metrics,
+                                                 const gnca_graph_diag_out* diag);
+int gnca_rollout_trace_vitals(const gnca_step_desc* desc, const gnca_weights* w, const gnca_trace_args* args,
+                              const gnca_trace_metrics* metrics, const gnca_graph_diag_out* diag,
+                              const gnca_trace_vitals* vitals, const float* x, float* x_final, void* ws,
+                              size_t ws_bytes, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Step-adjacent batch op: damage (src/utils/damage.py:15-138).  ONE damage kind for the whole
  * batch, in place on the [B,C,H,W] state, with the random draws supplied by the caller (device
  * memory), so a whole batch is one launch with no host round trip per sample.
