@@ -116,6 +116,18 @@ class MaskedLossDesc(ctypes.Structure):
                 ("lam_bg_rgb", ctypes.c_float), ("close_thresh", ctypes.c_float), ("close_steps", ctypes.c_int32)]
 
 
+TAP_PREMULT, TAP_MASKED = 0, 1
+TAP_CHUNK = 32   # taps per launch of the tap loss kernel (include/gnca.h)
+
+
+class RolloutTaps(ctypes.Structure):
+    """Mirror of gnca_rollout_taps (include/gnca.h): steps is a HOST array read during the call, target a
+    device pointer; the stream travels in the descriptor."""
+    _fields_ = [("n", ctypes.c_int32), ("steps", ctypes.c_void_p), ("kind", ctypes.c_int32),
+                ("masked", MaskedLossDesc), ("target", ctypes.c_void_p), ("target_bstride", ctypes.c_int64),
+                ("stream", ctypes.c_void_p)]
+
+
 OPTIM_MAX_TENSORS = 24
 OPTIM_ONE_LAUNCH_MAX = 65536   # elements a one-launch gnca_optim_step call may hold (include/gnca.h)
 OPTIM_POLICY_NONE, OPTIM_POLICY_NORMALIZE, OPTIM_POLICY_CLIP = 0, 1, 2
@@ -199,7 +211,8 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_graph_diag_workspace_bytes", "gnca_graph_diag", "gnca_rollout_trace_diag_workspace_bytes",
            "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy",
            "gnca_state_vitals_workspace_bytes", "gnca_state_vitals",
-           "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals")
+           "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals",
+           "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -360,6 +373,15 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_trace_vitals.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                       ctypes.POINTER(TraceArgs), ctypes.POINTER(TraceMetrics), do,
                                                       ctypes.POINTER(TraceVitals), vp, vp, vp, sz, vp]
+        if hasattr(lib, "gnca_rollout_tap_loss"):   # (likewise)
+            tp = ctypes.POINTER(RolloutTaps)
+            lib.gnca_rollout_tap_loss.restype = ctypes.c_int
+            lib.gnca_rollout_tap_loss.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(RolloutSched), tp, vp, sz,
+                                                  vp, vp, vp]
+            lib.gnca_rollout_bwd_taps.restype = ctypes.c_int
+            lib.gnca_rollout_bwd_taps.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                  ctypes.POINTER(RolloutSched), tp, vp, sz, vp, vp, vp, vp, vp,
+                                                  ctypes.POINTER(Grads), vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -368,14 +368,11 @@ __global__ __launch_bounds__(kThreads) void gnca_damage_policy_k(const gnca_dama
 }
 
 // loss_premult_rgba (train_graph_augmented_nca.py:52-61): one workgroup per sample, fixed-order
-// fp64 reduction (deterministic)
-__global__ __launch_bounds__(kThreads) void gnca_loss_fwd(int H, int W, const float* pred, long pbs,
-                                                          const float* tgt, long tbs, float* out) {
-  __shared__ double red[kThreads / 64];
-  const int b = blockIdx.x, tid = threadIdx.x;
+// fp64 reduction (deterministic).  The per-sample body, shared with gnca_tap_loss: the value is
+// returned in thread 0 (red: one slot per wave).
+__device__ __forceinline__ float premult_loss_sample(int H, int W, const float* p, const float* t, double* red) {
+  const int tid = threadIdx.x;
   const size_t HW = (size_t)H * W;
-  const float* p = pred + (size_t)b * pbs;
-  const float* t = tgt + (size_t)b * tbs;
   double acc = 0.0;
   for (size_t e = tid; e < HW; e += kThreads) {
     const float a = p[3 * HW + e];
@@ -390,11 +387,36 @@ __global__ __launch_bounds__(kThreads) void gnca_loss_fwd(int H, int W, const fl
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
+  double v = 0.0;
   if (tid == 0) {
-    double v = 0.0;
     for (int w = 0; w < kThreads / 64; ++w) v += red[w];
-    out[b] = (float)(v / (4.0 * (double)HW));
+    v = v / (4.0 * (double)HW);
   }
+  return (float)v;
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_loss_fwd(int H, int W, const float* pred, long pbs,
+                                                          const float* tgt, long tbs, float* out) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.x;
+  const float v = premult_loss_sample(H, W, pred + (size_t)b * pbs, tgt + (size_t)b * tbs, red);
+  if (threadIdx.x == 0) out[b] = v;
+}
+
+// g * d loss_premult / d pred at cell q of one sample: the four channel values, in fp32.  Shared
+// with gnca_tap_inject.
+__device__ __forceinline__ void premult_grad_cell(size_t HW, const float* p, const float* t, size_t q, float g,
+                                                  float v[4]) {
+  const float s = g * (float)(2.0 / (4.0 * (double)HW));
+  const float a = p[3 * HW + q];
+  float ga = a - t[3 * HW + q];
+  for (int c = 0; c < 3; ++c) {
+    const float x = p[c * HW + q];
+    const float r = x * a - t[c * HW + q];
+    v[c] = s * r * a;
+    ga = fmaf(r, x, ga);
+  }
+  v[3] = s * ga;
 }
 
 __global__ __launch_bounds__(kThreads) void gnca_loss_bwd(int B, int H, int W, const float* pred, long pbs,
@@ -403,19 +425,10 @@ __global__ __launch_bounds__(kThreads) void gnca_loss_bwd(int B, int H, int W, c
   const size_t HW = (size_t)H * W, total = (size_t)B * HW;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
     const size_t b = e / HW, q = e - b * HW;
-    const float* p = pred + b * pbs;
-    const float* t = tgt + b * tbs;
     float* o = gp + b * gbs;
-    const float s = g[b] * (float)(2.0 / (4.0 * (double)HW));
-    const float a = p[3 * HW + q];
-    float ga = a - t[3 * HW + q];
-    for (int c = 0; c < 3; ++c) {
-      const float x = p[c * HW + q];
-      const float r = x * a - t[c * HW + q];
-      o[c * HW + q] = s * r * a;
-      ga = fmaf(r, x, ga);
-    }
-    o[3 * HW + q] = s * ga;
+    float v[4];
+    premult_grad_cell(HW, pred + b * pbs, tgt + b * tbs, q, g[b], v);
+    for (int c = 0; c < 4; ++c) o[c * HW + q] = v[c];
   }
 }
 
@@ -438,14 +451,12 @@ __device__ inline double block_sum(double v, double* red) {
   return s;
 }
 
-__global__ __launch_bounds__(kThreads) void gnca_masked_loss_fwd(const gnca_masked_loss_desc d, const float* pred,
-                                                                 long pbs, const float* tgt, long tbs, float* out,
-                                                                 int32_t* alive_count, int32_t* nsteps_out) {
-  __shared__ double red[kThreads / 64];
-  const int b = blockIdx.x, tid = threadIdx.x;
+// The per-sample body of the masked loss, shared with gnca_tap_loss: every thread returns the value
+// and the alive count (block_sum leaves each sum in all threads); thread 0 of the caller stores them.
+__device__ __forceinline__ float masked_loss_sample(const gnca_masked_loss_desc& d, const float* p, const float* t,
+                                                    double* red, int32_t* count) {
+  const int tid = threadIdx.x;
   const size_t HW = (size_t)d.H * d.W;
-  const float* p = pred + (size_t)b * pbs;
-  const float* t = tgt + (size_t)b * tbs;
   double prim = 0.0, bga = 0.0, bgrgb = 0.0, area = 0.0, cnt = 0.0;
   for (size_t e = tid; e < HW; e += kThreads) {
     const float ta = t[3 * HW + e], pa = p[3 * HW + e];
@@ -469,15 +480,44 @@ __global__ __launch_bounds__(kThreads) void gnca_masked_loss_fwd(const gnca_mask
   bgrgb = block_sum(bgrgb, red);
   area = block_sum(area, red);
   cnt = block_sum(cnt, red);   // (integers below 2^53: exact)
-  if (tid == 0) {
-    const double hw = (double)HW;
-    const double v = prim / (cnt + 1e-8) + (double)d.lam_bg_alpha * bga / hw +
-                     (double)d.lam_bg_rgb * bgrgb / (3.0 * hw) + (double)d.lam_area * area / hw;
-    const float vf = (float)v;
+  const double hw = (double)HW;
+  const double v = prim / (cnt + 1e-8) + (double)d.lam_bg_alpha * bga / hw +
+                   (double)d.lam_bg_rgb * bgrgb / (3.0 * hw) + (double)d.lam_area * area / hw;
+  *count = (int32_t)cnt;
+  return (float)v;
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_masked_loss_fwd(const gnca_masked_loss_desc d, const float* pred,
+                                                                 long pbs, const float* tgt, long tbs, float* out,
+                                                                 int32_t* alive_count, int32_t* nsteps_out) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.x;
+  int32_t cnt;
+  const float vf = masked_loss_sample(d, pred + (size_t)b * pbs, tgt + (size_t)b * tbs, red, &cnt);
+  if (threadIdx.x == 0) {
     out[b] = vf;
-    alive_count[b] = (int32_t)cnt;
+    alive_count[b] = cnt;
     if (nsteps_out) nsteps_out[b] = vf < d.close_thresh ? d.close_steps : 0;
   }
+}
+
+// g * d masked_loss / d pred at cell q of one sample (n: its alive count): the four channel values, in
+// fp32.  Shared with gnca_tap_inject.
+__device__ __forceinline__ void masked_grad_cell(const gnca_masked_loss_desc& d, size_t HW, const float* p,
+                                                 const float* t, size_t q, float g, int32_t n, float v[4]) {
+  const double hw = (double)HW;
+  const double gb = (double)g;
+  const float s = (float)(2.0 * gb / ((double)n + 1e-8));   // (unused where nothing is alive)
+  const float ta = t[3 * HW + q], pa = p[3 * HW + q];
+  const bool alive = ta > d.alpha_thr;
+  const float pen_a = (float)(gb * ((alive ? 0.0 : (double)d.lam_bg_alpha) + (double)d.lam_area) / hw);
+  const float pen_c = alive ? 0.f : (float)(gb * (double)d.lam_bg_rgb / (3.0 * hw));
+  for (int c = 0; c < 3; ++c) {
+    const float x = p[c * HW + q];
+    const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);   // torch's abs gradient: sign(0) = 0
+    v[c] = alive ? s * (x - t[c * HW + q]) : pen_c * sg;
+  }
+  v[3] = alive ? fmaf(s, pa - ta, pen_a) : pen_a;
 }
 
 __global__ __launch_bounds__(kThreads) void gnca_masked_loss_bwd(const gnca_masked_loss_desc d, const float* pred,
@@ -485,24 +525,101 @@ __global__ __launch_bounds__(kThreads) void gnca_masked_loss_bwd(const gnca_mask
                                                                  const int32_t* alive_count, const float* g,
                                                                  float* gp, long gbs) {
   const size_t HW = (size_t)d.H * d.W, total = (size_t)d.B * HW;
-  const double hw = (double)HW;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
     const size_t b = e / HW, q = e - b * HW;
-    const float* p = pred + b * pbs;
-    const float* t = tgt + b * tbs;
     float* o = gp + b * gbs;
-    const double gb = (double)g[b];
-    const float s = (float)(2.0 * gb / ((double)alive_count[b] + 1e-8));   // (unused where nothing is alive)
-    const float ta = t[3 * HW + q], pa = p[3 * HW + q];
-    const bool alive = ta > d.alpha_thr;
-    const float pen_a = (float)(gb * ((alive ? 0.0 : (double)d.lam_bg_alpha) + (double)d.lam_area) / hw);
-    const float pen_c = alive ? 0.f : (float)(gb * (double)d.lam_bg_rgb / (3.0 * hw));
-    for (int c = 0; c < 3; ++c) {
-      const float x = p[c * HW + q];
-      const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);   // torch's abs gradient: sign(0) = 0
-      o[c * HW + q] = alive ? s * (x - t[c * HW + q]) : pen_c * sg;
+    float v[4];
+    masked_grad_cell(d, HW, pred + b * pbs, tgt + b * tbs, q, g[b], alive_count[b], v);
+    for (int c = 0; c < 4; ++c) o[c * HW + q] = v[c];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Taps: the two losses above on intermediate states of a rollout, read from its tape in place
+// (gnca_rollout_tap_loss), and their gradients added to the backward's running cotangent
+// (gnca_rollout_bwd_taps; the host loop is in gnca_bwd.hip).  Both kernels read 8 planes of
+// a state once, threads along the cells of a plane (coalesced), and are traffic-bound.
+// ---------------------------------------------------------------------------------------------
+struct TapChunk {
+  int first;                  // index r of the chunk's first tap
+  int step[GNCA_TAP_CHUNK];   // the tapped step of each tap of the chunk (grid.y of them are read)
+};
+
+struct TapLossArgs {
+  gnca_masked_loss_desc m;    // B, H, W (and the knobs of the masked kind)
+  int T;
+  const char* tape;
+  size_t slot;                // bytes between two tape slots
+  size_t sstride;             // a state's sample stride, C*H*W floats
+  const float* x_final;       // the state after step T (not on the tape)
+  const float* tgt;
+  long tbs;
+  float* losses;              // [R][B]
+  int32_t* alive_count;       // [B], masked only
+};
+
+// grid (B, taps of the chunk): one workgroup per (tap, sample)
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void gnca_tap_loss(const TapLossArgs a, const TapChunk ch) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.x, r = ch.first + (int)blockIdx.y, t = ch.step[blockIdx.y];
+  const float* state = t == a.T ? a.x_final : reinterpret_cast<const float*>(a.tape + (size_t)t * a.slot);
+  const float* p = state + (size_t)b * a.sstride;
+  const float* tg = a.tgt + (size_t)b * a.tbs;
+  if (KIND == GNCA_TAP_PREMULT) {
+    const float v = premult_loss_sample(a.m.H, a.m.W, p, tg, red);
+    if (threadIdx.x == 0) a.losses[(size_t)r * a.m.B + b] = v;
+  } else {
+    int32_t cnt;
+    const float v = masked_loss_sample(a.m, p, tg, red, &cnt);
+    if (threadIdx.x == 0) {
+      a.losses[(size_t)r * a.m.B + b] = v;
+      if (r == 0) a.alive_count[b] = cnt;   // (the target's alone: the same at every tap)
     }
-    o[3 * HW + q] = alive ? fmaf(s, pa - ta, pen_a) : pen_a;
+  }
+}
+
+// one rounded fp32 add: the pragma keeps it out of an FMA with the product that feeds it
+__device__ __forceinline__ float add_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+
+struct TapInjectArgs {
+  gnca_masked_loss_desc m;
+  int C;
+  const float* state;         // S_t [B,C,H,W]
+  const float* tgt;
+  long tbs;
+  const int32_t* alive_count;
+  const float* gl;            // g_losses[r] [B]
+  const float* src;           // FULL: the cotangent the gradient is added to, or null (zeros)
+  float* dst;                 // [B,C,H,W]
+};
+
+// one thread per cell (b, q).  !FULL: dst[b, c<4, q] += v.  FULL: every channel of dst is written,
+// src + v on channels 0..3 and src on the rest (src == null: v and zeros).
+template <int KIND, bool FULL>
+__global__ __launch_bounds__(kThreads) void gnca_tap_inject(const TapInjectArgs a) {
+  const size_t HW = (size_t)a.m.H * a.m.W, total = (size_t)a.m.B * HW, ss = (size_t)a.C * HW;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
+    const size_t b = e / HW, q = e - b * HW;
+    const float* p = a.state + b * ss;
+    const float* tg = a.tgt + b * a.tbs;
+    float v[4];
+    if (KIND == GNCA_TAP_PREMULT) premult_grad_cell(HW, p, tg, q, a.gl[b], v);
+    else masked_grad_cell(a.m, HW, p, tg, q, a.gl[b], a.alive_count[b], v);
+    float* o = a.dst + b * ss + q;
+    if (!FULL) {
+      for (int c = 0; c < 4; ++c) o[c * HW] = add_rn(o[c * HW], v[c]);
+    } else if (a.src != nullptr) {
+      const float* s = a.src + b * ss + q;
+      for (int c = 0; c < 4; ++c) o[c * HW] = add_rn(s[c * HW], v[c]);
+      for (int c = 4; c < a.C; ++c) o[c * HW] = s[c * HW];
+    } else {
+      for (int c = 0; c < 4; ++c) o[c * HW] = v[c];
+      for (int c = 4; c < a.C; ++c) o[c * HW] = 0.f;
+    }
   }
 }
 
@@ -1220,6 +1337,76 @@ extern "C" int gnca_loss_masked_bwd_f32(const gnca_masked_loss_desc* d, const fl
                      grad_pred, (long)gbs);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+namespace gnca {
+
+bool taps_ok(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps) {
+  if (!d || !s || !taps || !taps->steps || !taps->target || taps->n < 1 || taps->target_bstride < 0) return false;
+  if (d->B <= 0 || d->C < 4 || d->H <= 0 || d->W <= 0) return false;
+  if (taps->kind != GNCA_TAP_PREMULT && taps->kind != GNCA_TAP_MASKED) return false;
+  if (taps->masked.B != d->B || taps->masked.H != d->H || taps->masked.W != d->W) return false;   // (either kind)
+  int prev = 0;
+  for (int r = 0; r < taps->n; ++r) {
+    const int t = taps->steps[r];
+    if (t <= prev || t > s->steps) return false;
+    prev = t;
+  }
+  return true;
+}
+
+int launch_tap_inject(const gnca_step_desc* d, const gnca_rollout_taps* taps, const float* state, const float* gl,
+                      const int32_t* alive_count, const float* src, float* dst, bool full, hipStream_t st) {
+  TapInjectArgs a;
+  a.m = taps->masked;   // (B, H, W are the desc's: taps_ok)
+  a.C = d->C;
+  a.state = state; a.tgt = taps->target; a.tbs = (long)taps->target_bstride;
+  a.alive_count = alive_count; a.gl = gl; a.src = src; a.dst = dst;
+  const dim3 grid(elementwise_blocks((size_t)d->B * d->H * d->W)), block(kThreads);
+  const bool masked = taps->kind == GNCA_TAP_MASKED;
+  if (masked && full) hipLaunchKernelGGL((gnca_tap_inject<GNCA_TAP_MASKED, true>), grid, block, 0, st, a);
+  else if (masked) hipLaunchKernelGGL((gnca_tap_inject<GNCA_TAP_MASKED, false>), grid, block, 0, st, a);
+  else if (full) hipLaunchKernelGGL((gnca_tap_inject<GNCA_TAP_PREMULT, true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((gnca_tap_inject<GNCA_TAP_PREMULT, false>), grid, block, 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+}  // namespace gnca
+
+extern "C" int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                     const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes,
+                                     const float* x_final, float* losses, int32_t* alive_count) {
+  if (!taps_ok(desc, sched, taps) || !x_final || !losses) return GNCA_ERR_INVALID;
+  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  TapeLayout L;
+  if (!tape_layout(desc, sched, &L)) return GNCA_ERR_INVALID;
+  if (!tape) return GNCA_ERR_INVALID;
+  if (tape_bytes < L.bytes) return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(taps->stream);
+  StreamDeviceGuard dg(st);
+  TapLossArgs a;
+  a.m = taps->masked;   // (B, H, W are the desc's: taps_ok)
+  a.T = sched->steps;
+  a.tape = reinterpret_cast<const char*>(tape);
+  a.slot = L.slot;
+  a.sstride = (size_t)desc->C * desc->H * desc->W;
+  a.x_final = x_final;
+  a.tgt = taps->target; a.tbs = (long)taps->target_bstride;
+  a.losses = losses; a.alive_count = alive_count;
+  for (int first = 0; first < taps->n; first += GNCA_TAP_CHUNK) {
+    TapChunk ch;
+    ch.first = first;
+    const int n = taps->n - first < GNCA_TAP_CHUNK ? taps->n - first : GNCA_TAP_CHUNK;
+    for (int j = 0; j < GNCA_TAP_CHUNK; ++j) ch.step[j] = j < n ? taps->steps[first + j] : 0;
+    const dim3 grid((unsigned)desc->B, (unsigned)n), block(kThreads);
+    if (taps->kind == GNCA_TAP_MASKED) hipLaunchKernelGGL(gnca_tap_loss<GNCA_TAP_MASKED>, grid, block, 0, st, a, ch);
+    else hipLaunchKernelGGL(gnca_tap_loss<GNCA_TAP_PREMULT>, grid, block, 0, st, a, ch);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  }
   return GNCA_OK;
 }
 

@@ -2470,10 +2470,42 @@ size_t gnca_rollout_bwd_workspace_bytes(const gnca_step_desc* desc, const gnca_r
   return roll_bwd_layout(desc, sched, &R) ? R.bytes : 0;
 }
 
-int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
-                         const void* tape, size_t tape_bytes, const float* gy, float* gx,
-                         const gnca_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  if (!desc || !w || !sched || !gy || !gx || gx == gy) return GNCA_ERR_INVALID;
+// Zero a block of the accumulating rows with a kernel: `n` 16-byte vectors (every block is a multiple
+// of 256 bytes on a 256-byte boundary).  gnca_rollout_bwd_taps only; gnca_rollout_bwd_f32 keeps its
+// three hipMemsetAsync calls.  A capture records those as memset nodes, and on the second launch of
+// the instantiated graph the rows they should have zeroed were dirty; a kernel
+// node is not affected, and gnca_rollout_bwd_taps has to work under capture.
+static __global__ __launch_bounds__(kThreads) void gnca_b_zero(f4* p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads)
+    p[i] = f4{0.f, 0.f, 0.f, 0.f};
+}
+
+static int zero_rows(void* p, size_t bytes, hipStream_t st) {
+  const size_t n = bytes / sizeof(f4);
+  if (n == 0) return GNCA_OK;
+  const size_t blocks = (n + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(gnca_b_zero, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(kThreads), 0, st,
+                     reinterpret_cast<f4*>(p), n);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+// the taps of gnca_rollout_bwd_taps (validated by the caller: taps_ok, g_losses != null)
+struct TapsBwd {
+  const gnca_rollout_taps* taps;
+  const float* x_final;
+  const float* g_losses;
+  const int32_t* alive_count;
+};
+
+// The body of gnca_rollout_bwd_f32 (tb == nullptr: exactly its launches) and of gnca_rollout_bwd_taps
+// (tb != nullptr: each tap's loss gradient joins the running cotangent between two steps; gy may
+// then be null, a zero cotangent of x_final).
+static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                            const void* tape, size_t tape_bytes, const float* gy, float* gx,
+                            const gnca_grads* grads, void* ws, size_t ws_bytes, void* stream, const TapsBwd* tb) {
+  if (!desc || !w || !sched || (!gy && !tb) || !gx || gx == gy) return GNCA_ERR_INVALID;
   RollBwdLayout R;
   if (!roll_bwd_layout(desc, sched, &R)) return GNCA_ERR_INVALID;
   const int T = sched->steps;
@@ -2495,9 +2527,14 @@ int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
   acc.pq = R.att ? reinterpret_cast<double*>(wsb + R.off_pq) : nullptr;
   int rc;
   // the rows start at zero, once per rollout
-  if (hipMemsetAsync(acc.pb, 0, R.pb_bytes, st) != hipSuccess || hipMemsetAsync(acc.pa, 0, R.pa_bytes, st) != hipSuccess ||
-      (acc.pq && hipMemsetAsync(acc.pq, 0, R.pq_bytes, st) != hipSuccess))
-    return GNCA_ERR_HIP;
+  if (!tb) {
+    if (hipMemsetAsync(acc.pb, 0, R.pb_bytes, st) != hipSuccess || hipMemsetAsync(acc.pa, 0, R.pa_bytes, st) != hipSuccess ||
+        (acc.pq && hipMemsetAsync(acc.pq, 0, R.pq_bytes, st) != hipSuccess))
+      return GNCA_ERR_HIP;
+  } else if ((rc = zero_rows(acc.pb, R.pb_bytes, st)) != GNCA_OK || (rc = zero_rows(acc.pa, R.pa_bytes, st)) != GNCA_OK ||
+             (acc.pq && (rc = zero_rows(acc.pq, R.pq_bytes, st)) != GNCA_OK)) {
+    return rc;
+  }
   if (T == 0) {
     if (hipMemcpyAsync(gx, gy, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
   } else if (sched->nsteps &&
@@ -2506,7 +2543,25 @@ int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
   }
   const bool recompute = (sched->flags & GNCA_SCHED_RECOMPUTE) != 0;
   const float* g = gy;
-  for (int t = T - 1; t >= 0; --t) {
+  int t_first = T - 1;                     // the first step whose backward runs
+  int r = tb ? tb->taps->n - 1 : -1;       // the next tap, walking the list backwards
+  if (tb) {
+    // A tap at T, or no gy: the first cotangent buffer is written whole (gy + the tap's gradient, or
+    // the gradient and zeros), so gy is never modified and nothing is copied.  Without gy the steps
+    // after the last tap are not run: their cotangent is zero.
+    const int tl = tb->taps->steps[r];
+    if (tl == T || !gy) {
+      const float* state = tl == T ? tb->x_final : reinterpret_cast<const float*>(tp + (size_t)tl * R.T.slot);
+      float* first = gb[tl & 1];
+      rc = launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count,
+                             tl == T ? gy : nullptr, first, true, st);
+      if (rc != GNCA_OK) return rc;
+      g = first;
+      t_first = tl - 1;
+      --r;
+    }
+  }
+  for (int t = t_first; t >= 0; --t) {
     gnca_step_desc sd;
     sched_step_desc(desc, sched, t, &sd);
     const float* xt = reinterpret_cast<const float*>(tp + (size_t)t * R.T.slot);
@@ -2516,6 +2571,12 @@ int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
                        nullptr, saved, wsb + R.off_step, R.step_bytes, stream, &acc);
     if (rc != GNCA_OK) return rc;
     g = out;
+    if (r >= 0 && tb->taps->steps[r] == t) {   // dL/dS_t is complete but for this tap (t >= 1: out is gb[t & 1])
+      rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out, false,
+                             st);
+      if (rc != GNCA_OK) return rc;
+      --r;
+    }
   }
   if (!grads) return GNCA_OK;
   // one reduction of each row block per rollout
@@ -2555,6 +2616,24 @@ int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
     if ((rc = r.launch(st)) != GNCA_OK) return rc;
   }
   return GNCA_OK;
+}
+
+int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const void* tape, size_t tape_bytes, const float* gy, float* gx,
+                         const gnca_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  return rollout_bwd_impl(desc, w, sched, tape, tape_bytes, gy, gx, grads, ws, ws_bytes, stream, nullptr);
+}
+
+int gnca_rollout_bwd_taps(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                          const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes, const float* x_final,
+                          const float* gy, const float* g_losses, const int32_t* alive_count, float* gx,
+                          const gnca_grads* grads, void* ws, size_t ws_bytes) {
+  if (!taps_ok(desc, sched, taps) || !x_final || (!gy && !g_losses) || !gx || gx == gy) return GNCA_ERR_INVALID;
+  if (g_losses && taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  const TapsBwd tb = {taps, x_final, g_losses, alive_count};
+  // (no g_losses: the taps contribute nothing, the launches are gnca_rollout_bwd_f32's)
+  return rollout_bwd_impl(desc, w, sched, tape, tape_bytes, gy, gx, grads, ws, ws_bytes, taps->stream,
+                          g_losses ? &tb : nullptr);
 }
 
 }  // extern "C"

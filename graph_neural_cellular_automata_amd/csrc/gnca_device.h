@@ -342,6 +342,16 @@ bool tape_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, TapeLayou
 // masks[t][b] = t < full_steps || t < nsteps[b] (uint8 [T][B]), one launch
 int launch_nsteps_masks(const int32_t* nsteps, int B, int T, int full_steps, uint8_t* masks, hipStream_t st);
 
+// The tap list of gnca_rollout_tap_loss / gnca_rollout_bwd_taps, validated (gnca_aux.hip)
+bool taps_ok(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps);
+
+// One tap's loss gradient into the backward's running cotangent (gnca_tap_inject, gnca_aux.hip).
+// state: S_t [B,C,H,W]; gl: g_losses[r] [B].  full == false: dst[b, c<4] += v in place (the other
+// channels are not touched).  full == true: dst is written whole, src + v on channels 0..3 and src
+// on the rest (src == nullptr: v and zeros).
+int launch_tap_inject(const gnca_step_desc* d, const gnca_rollout_taps* taps, const float* state, const float* gl,
+                      const int32_t* alive_count, const float* src, float* dst, bool full, hipStream_t st);
+
 // hipError_t of the last failed launch on this thread (gnca_last_hip_error)
 extern thread_local int g_last_hip;
 

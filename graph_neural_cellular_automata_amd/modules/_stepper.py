@@ -357,6 +357,120 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
     return out
 
 
+class _RolloutObjectiveFn(torch.autograd.Function):
+    """A whole rollout AND the per-sample losses of its tapped states as ONE autograd node with two
+    outputs: ``gnca_rollout_fwd_f32`` with a tape and ``gnca_rollout_tap_loss`` on that tape forward,
+    ``gnca_rollout_bwd_taps`` backward.  Either output's cotangent may be absent (no zero tensor is
+    made for it); the parameter gradients leave through the packs as in ``_RolloutFn``."""
+
+    @staticmethod
+    def forward(ctx, x, call, taps, weights, keep, core, graph, tok_core, tok_graph, tensors=None):
+        ctx.set_materialize_grads(False)
+        out, tape = call.forward(weights, x, want_tape=True)
+        losses, alive = call.tap_losses(taps, tape, out)
+        ctx.call, ctx.taps, ctx.weights, ctx.keep, ctx.tape, ctx.alive = call, taps, weights, keep, tape, alive
+        ctx.packs = (core, graph)
+        ctx.save_for_backward(out)   # (the state of a tap at the last step: it is not on the tape)
+        ctx.versions = tuple((t, t._version) for t in (tensors or {}).values())
+        return out, losses
+
+    @staticmethod
+    def backward(ctx, g_final, g_losses):
+        for t, v in ctx.versions:
+            if t._version != v:
+                raise RuntimeError(
+                    "one of the variables needed for gradient computation has been modified by an "
+                    f"inplace operation: a rollout weight of shape {tuple(t.shape)} is at version "
+                    f"{t._version}; expected version {v} instead")
+        if ctx.tape is None:
+            raise RuntimeError("rollout_objective: backward through the same rollout a second time "
+                               "(its tape was freed)")
+        if g_final is None and g_losses is None:
+            ctx.tape = None
+            return (None,) * 10
+        (x_final,) = ctx.saved_tensors
+        desc = ctx.call.desc
+        no_graph_use = (desc.flags & L.GRAPH) and desc.num_offsets == 0
+        want, views, flats = {}, {}, [None, None]
+        for i, pack in enumerate(ctx.packs):
+            if pack is None or not ctx.needs_input_grad[7 + i] or (i == 1 and no_graph_use):
+                continue
+            flats[i] = torch.empty(sum(pack.sizes), dtype=torch.float32, device=x_final.device)
+            views.update(pack.views(flats[i]))
+            want.update(zip(pack.names, pack.params))
+        gx, _ = ctx.call.backward_taps(ctx.weights, ctx.taps, ctx.tape, x_final,
+                                       None if g_final is None else g_final.contiguous(),
+                                       None if g_losses is None else g_losses.contiguous(), ctx.alive,
+                                       want=want, out=views)
+        ctx.tape = None
+        return (gx if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, flats[0], flats[1],
+                None)
+
+
+class RolloutObjective:
+    """What ``rollout_objective()`` returns: ``x_final`` [B,C,H,W], exactly ``rollout()``'s result;
+    ``losses`` float32 [R,B], the per-sample loss of the state after each tapped step; ``steps``, the R
+    tapped step indices (from 1).  ``x_final`` and ``losses`` are the two outputs of one autograd node."""
+
+    __slots__ = ("x_final", "losses", "steps")
+
+    def __init__(self, x_final, losses, steps):
+        self.x_final, self.losses, self.steps = x_final, losses, steps
+
+    def __repr__(self):
+        return f"RolloutObjective(steps={self.steps}, losses={tuple(self.losses.shape)})"
+
+
+def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target, graph, hidden_only: bool, *,
+                          every=1, record=None, loss="premult", alpha_thr=0.2, lam_area=5e-5, lam_bg_alpha=0.0,
+                          lam_bg_rgb=0.0, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0, fire=None,
+                          seed=None, sample_base=0, offsets=None, recompute=False) -> RolloutObjective:
+    """The shared body of ``NeuralCA.rollout_objective`` / ``NeuralCAGraph.rollout_objective``."""
+    from .. import loss as LS
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    B, C, H, W = x.shape
+    _check_norm(model)
+    # validation first (pure Python): nothing below runs, and no offsets are drawn, on a bad call
+    if loss not in S.TAP_KINDS:
+        raise ValueError(f"loss must be one of {sorted(S.TAP_KINDS)}, got {loss!r}")
+    if C < 4:
+        raise ValueError(f"the losses read channels 0..3 of the state, which has {C}")
+    _, target = LS._prepare(x[:, :4], target)
+    knobs = None
+    if loss == "masked":
+        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
+                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    rec = S.expand_record(steps, every, record)
+    if not rec:
+        raise ValueError("record is empty: a rollout objective needs at least one tapped step")
+    x = S.check_state(x, model.n_channels)   # (channels, device, dtype: before the schedule draws its offsets)
+    tensors = _step_tensors(model, graph)
+    grad = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors.values()))
+    # (without grad the tape is only read by the loss kernel: states alone)
+    sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                             sample_base=sample_base, offsets=offsets,
+                             sample_offsets=None if graph is None else graph.sample_offsets,
+                             recompute=recompute if grad else True)
+    desc, w, keep, tensors = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+    tgt = target.detach().to(x.device, torch.float32)
+    tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
+    call, taps = S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt)
+    if grad:
+        core, gpack = param_packs(model, tensors)
+        tc = core.token if core is not None else None
+        tg = gpack.token if gpack is not None else None
+        out, losses = _RolloutObjectiveFn.apply(x, call, taps, w, keep, core, gpack, tc, tg, tensors)
+    else:
+        out, tape = call.forward(w, x, want_tape=True)
+        losses, _ = call.tap_losses(taps, tape, out)
+        del tape
+    return RolloutObjective(out, losses, list(rec))
+
+
 class TraceResult:
     """What ``trace()`` returns: ``x_final`` [B,C,H,W], ``frames`` [R,B,channels,H,W] (the state after
     each recorded step), ``steps`` (the R recorded step indices, counted from 1 within this call) and

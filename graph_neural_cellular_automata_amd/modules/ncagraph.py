@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import TraceResult, run_rollout, run_step, run_trace
+from ._stepper import RolloutObjective, TraceResult, run_rollout, run_rollout_objective, run_step, run_trace
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -94,6 +94,41 @@ class NeuralCAGraph(nn.Module):
                            message_gain=self.message_gain if message_gain is None else message_gain,
                            nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
                            offsets=offsets, recompute=recompute)
+
+    def rollout_objective(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, every: int = 1, record=None,
+                          loss: str = "premult", alpha_thr: float = 0.2, lam_area: float = 5e-5,
+                          lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0, fire_rate=1.0, message_gain=None,
+                          nsteps=None, min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
+                          offsets=None, recompute: bool = False) -> RolloutObjective:
+        """``rollout()`` that also returns per-sample losses at intermediate steps, as ONE autograd node
+        (extension, not in the reference): the trainers' supervision of several steps of one rollout
+        without a chain of ``rollout()`` + loss nodes.
+
+        Returns a ``RolloutObjective``: ``x_final`` [B,C,H,W], exactly ``rollout()``'s result;
+        ``losses`` float32 [R,B], the loss of the state after each tapped step; ``steps``, the R tapped
+        step indices.  The taps follow ``trace()``'s rules: ``every=n`` taps steps ``n, 2n, ...`` and
+        also ``steps`` when it is not a multiple, ``record`` lists them instead (strictly increasing, in
+        ``1..steps``).  ``loss="premult"`` is ``loss_premult_rgba(state[:, :4], target)``,
+        ``loss="masked"`` is ``masked_loss(state[:, :4], target, alpha_thr, lam_area, lam_bg_alpha,
+        lam_bg_rgb)``, bitwise; ``target`` is [4,H,W], [1,4,H,W] or [B,4,H,W].  Every other keyword is
+        ``rollout()``'s.  Bad arguments raise ``ValueError`` before anything is drawn or launched.
+
+        The losses are read from the rollout's tape in place and their gradients join the backward's
+        running cotangent between two steps; build any scalar from ``losses`` (a mean, per-tap
+        weights) and, if wanted, from ``x_final``, and call ``backward()`` once: ``x.grad`` is bitwise
+        that of the chain of ``rollout()`` segments with a loss on each segment's end.  A sample with
+        ``nsteps[b]`` below a tapped step contributes the loss of its frozen state.  A second backward
+        raises, as for ``rollout()``.
+
+        Under ``no_grad``, or when nothing requires grad, ``x_final`` and ``losses`` are still returned
+        (a states-only tape is recorded and freed); that is not the tuned no-grad path, which stays
+        ``trace(..., target=)``."""
+        return run_rollout_objective(self, x, steps, target, self.graph, self.hidden_only, every=every,
+                                     record=record, loss=loss, alpha_thr=alpha_thr, lam_area=lam_area,
+                                     lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate,
+                                     message_gain=self.message_gain if message_gain is None else message_gain,
+                                     nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                     sample_base=sample_base, offsets=offsets, recompute=recompute)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

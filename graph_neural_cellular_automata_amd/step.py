@@ -829,3 +829,84 @@ class RolloutCall:
                                       ws.data_ptr(), ws.numel(), stream_ptr(gy.device))
         L.check(rc, "gnca_rollout_bwd_f32")
         return gx, grads
+
+    # -----------------------------------------------------------------------------------------
+    # taps: losses of intermediate states read from the tape (gnca_rollout_tap_loss) and the BPTT
+    # that adds their gradients between two steps (gnca_rollout_bwd_taps)
+    # -----------------------------------------------------------------------------------------
+    def tap_losses(self, taps: "RolloutTaps", tape, x_final):
+        """(losses [R,B], alive_count [B] or None) of the tapped states of the rollout that recorded
+        ``tape`` and returned ``x_final``."""
+        fn = _tap_entry("gnca_rollout_tap_loss")
+        B, dev = self.desc.B, x_final.device
+        losses = torch.empty(taps.c.n, B, dtype=torch.float32, device=dev)
+        alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
+        taps.c.stream = stream_ptr(dev)
+        rc = fn(ctypes.byref(self.desc), ctypes.byref(self.c), ctypes.byref(taps.c), tape.data_ptr(), tape.numel(),
+                x_final.data_ptr(), losses.data_ptr(), _ptr(alive))
+        L.check(rc, "gnca_rollout_tap_loss")
+        return losses, alive
+
+    def backward_taps(self, weights, taps: "RolloutTaps", tape, x_final, gy, g_losses, alive,
+                      want: dict | None = None, out: dict | None = None):
+        """(gx, {name: grad}) of ``sum(g_losses * losses) + sum(gy * x_final)``; either cotangent may be
+        None (not both).  ``want`` / ``out`` as in ``backward``."""
+        fn = _tap_entry("gnca_rollout_bwd_taps")
+        if gy is None and g_losses is None:
+            raise ValueError("backward_taps needs gy, g_losses or both")
+        dev = x_final.device
+        gy = None if gy is None else _dev_f32(gy, "grad_output")
+        if g_losses is not None:
+            g_losses = _dev_f32(g_losses, "grad_losses")
+            if tuple(g_losses.shape) != (taps.c.n, self.desc.B):
+                raise ValueError(f"grad_losses must be [{taps.c.n},{self.desc.B}], got {tuple(g_losses.shape)}")
+        gx = torch.empty_like(x_final)
+        g = L.Grads()
+        given, grads = out or {}, {}
+        for name, p in (want or {}).items():
+            t = given.get(name)
+            if t is None:
+                t = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
+            grads[name] = t
+            setattr(g, GRAD_FIELDS[name], t.data_ptr())
+        ws = torch.empty(self._sizes(L.load().gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=dev)
+        taps.c.stream = stream_ptr(dev)
+        rc = fn(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c), ctypes.byref(taps.c),
+                tape.data_ptr(), tape.numel(), x_final.data_ptr(), _ptr(gy), _ptr(g_losses), _ptr(alive),
+                gx.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel())
+        L.check(rc, "gnca_rollout_bwd_taps")
+        return gx, grads
+
+
+def _tap_entry(name: str):
+    fn = getattr(L.load(), name, None)
+    if fn is None:
+        raise L.GncaError(f"libgnca.so at {L.LIB_PATH} has no {name}; rebuild it")
+    return fn
+
+
+TAP_KINDS = {"premult": L.TAP_PREMULT, "masked": L.TAP_MASKED}
+
+
+class RolloutTaps:
+    """The taps of one ``rollout_objective`` call: the C struct with its host step list and the device
+    target kept alive.  ``record``: the tapped step indices (``expand_record``); ``kind``: a key of
+    ``TAP_KINDS``; ``knobs``: (alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb) of the masked kind;
+    ``target``: float32 [B or 1,4,H,W] on the state's device, contiguous."""
+
+    def __init__(self, desc: L.StepDesc, record: list, kind: str, knobs, target: torch.Tensor):
+        if not record:
+            raise ValueError("a rollout objective needs at least one tapped step")
+        c = L.RolloutTaps()
+        c.n = len(record)
+        arr = (ctypes.c_int32 * len(record))(*record)
+        c.steps = ctypes.cast(arr, ctypes.c_void_p)
+        c.kind = TAP_KINDS[kind]
+        c.masked.B, c.masked.H, c.masked.W = desc.B, desc.H, desc.W
+        if knobs is not None:
+            c.masked.alpha_thr, c.masked.lam_area, c.masked.lam_bg_alpha, c.masked.lam_bg_rgb = knobs
+        c.target = target.data_ptr()
+        c.target_bstride = 0 if target.shape[0] == 1 else target.stride(0)
+        self.c, self.record, self._keep = c, list(record), (arr, target)

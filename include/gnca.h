@@ -787,6 +787,54 @@ int gnca_loss_stability_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pr
                                 int64_t grad_bstride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Losses at intermediate steps of one rollout ("taps"), read from the tape in place, and the BPTT
+ * that adds their gradients to the running cotangent between two steps.  Neither name carries the
+ * _f32 suffix and the stream travels in the descriptor, as in gnca_render_u8.
+ *
+ * Tap r is the state after step steps[r] (1..T): tape slot steps[r] of the rollout that wrote
+ * `tape`, or x_final (contiguous [B,C,H,W]) for steps[r] == T, which is not on the tape.
+ *   losses[r][b] = gnca_loss_premult_f32 / gnca_loss_masked_f32 of channels 0..3 of that state,
+ *                  bitwise (one 256-thread workgroup per (tap, sample), the same fixed-order sums).
+ *   alive_count  : GNCA_TAP_MASKED only, written once (it depends on the target alone).
+ * The tap list is a HOST array; it reaches the device in kernel arguments, GNCA_TAP_CHUNK taps per
+ * launch, so the calls work under stream capture and R has no cap.
+ *
+ * gnca_rollout_bwd_taps is gnca_rollout_bwd_f32 with
+ *   dL/dS_t[b, c<4] += g_losses[r][b] * d losses[r][b] / d S_t        at t = steps[r],
+ * each term the fp32 value of gnca_loss_premult_bwd_f32 / gnca_loss_masked_bwd_f32 and one rounded
+ * add (never contracted), applied after step t's backward and before step t-1's.  gy == NULL stands
+ * for a zero cotangent of x_final: the steps after the last tap are not run.  g_losses == NULL is
+ * gnca_rollout_bwd_f32.  gy is never written.  ws: gnca_rollout_bwd_workspace_bytes.
+ * GNCA_ERR_INVALID before any launch: a null taps / steps / target, n < 1, steps not strictly
+ * increasing or outside 1..sched->steps, an unknown kind, masked.B/H/W != desc's (either kind),
+ * a missing alive_count (GNCA_TAP_MASKED), gy and g_losses both NULL, gx aliasing gy.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_TAP_PREMULT 0
+#define GNCA_TAP_MASKED 1
+#define GNCA_TAP_CHUNK 32   /* taps per launch of the loss kernel */
+
+typedef struct gnca_rollout_taps {
+  int32_t n;                     /* R >= 1                                                       */
+  const int32_t* steps;          /* HOST [R], strictly increasing, in 1..sched->steps            */
+  int32_t kind;                  /* GNCA_TAP_*                                                   */
+  gnca_masked_loss_desc masked;  /* knobs of GNCA_TAP_MASKED; B, H, W must equal the desc's      */
+  const float* target;           /* DEVICE, [B or 1][4][H][W]                                    */
+  int64_t target_bstride;        /* as gnca_loss_premult_f32 (0 = one target for the batch)      */
+  void* stream;
+} gnca_rollout_taps;
+
+int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                          const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes,
+                          const float* x_final, float* losses /*[R][B]*/,
+                          int32_t* alive_count /*[B], GNCA_TAP_MASKED only*/);
+int gnca_rollout_bwd_taps(const gnca_step_desc* desc, const gnca_weights* w,
+                          const gnca_rollout_sched* sched, const gnca_rollout_taps* taps,
+                          const void* tape, size_t tape_bytes, const float* x_final,
+                          const float* gy /*or NULL = zeros*/, const float* g_losses /*[R][B] or NULL*/,
+                          const int32_t* alive_count, float* gx, const gnca_grads* grads, void* ws,
+                          size_t ws_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * The iteration's tail: gradient policy + Adam in one call, and the pool write-back in one call.
  * Neither name carries the _f32 suffix of the entry points above.
  * -------------------------------------------------------------------------------------------*/
