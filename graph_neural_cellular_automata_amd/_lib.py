@@ -60,13 +60,15 @@ class Grads(ctypes.Structure):
 
 class RolloutSched(ctypes.Structure):
     """Mirror of gnca_rollout_sched (include/gnca.h): offsets / fire_rate / message_gain are HOST
-    arrays read during the call, nsteps / fire are device pointers."""
+    arrays read during the call, nsteps / fire are device pointers; ckpt_every (read only with
+    SCHED_CHECKPOINT) sits in what was the padding after flags."""
     _fields_ = [("steps", ctypes.c_int32), ("full_steps", ctypes.c_int32), ("flags", ctypes.c_uint32),
-                ("offsets", ctypes.c_void_p), ("fire_rate", ctypes.c_void_p),
+                ("ckpt_every", ctypes.c_int32), ("offsets", ctypes.c_void_p), ("fire_rate", ctypes.c_void_p),
                 ("message_gain", ctypes.c_void_p), ("nsteps", ctypes.c_void_p), ("fire", ctypes.c_void_p)]
 
 
 SCHED_RECOMPUTE = 1 << 0
+SCHED_CHECKPOINT = 1 << 1   # the tape keeps every ckpt_every-th state; the backward re-runs segments
 
 
 class TraceArgs(ctypes.Structure):
@@ -212,7 +214,7 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy",
            "gnca_state_vitals_workspace_bytes", "gnca_state_vitals",
            "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals",
-           "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps")
+           "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps", "gnca_rollout_fwd_taps")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -382,6 +384,11 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_bwd_taps.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                   ctypes.POINTER(RolloutSched), tp, vp, sz, vp, vp, vp, vp, vp,
                                                   ctypes.POINTER(Grads), vp, sz]
+        if hasattr(lib, "gnca_rollout_fwd_taps"):   # (likewise)
+            lib.gnca_rollout_fwd_taps.restype = ctypes.c_int
+            lib.gnca_rollout_fwd_taps.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                  ctypes.POINTER(RolloutSched), ctypes.POINTER(RolloutTaps),
+                                                  vp, vp, vp, sz, vp, vp, vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

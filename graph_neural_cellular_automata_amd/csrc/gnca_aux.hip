@@ -1374,6 +1374,30 @@ int launch_tap_inject(const gnca_step_desc* d, const gnca_rollout_taps* taps, co
   return GNCA_OK;
 }
 
+// gnca_tap_loss for ONE tap whose state is given by address: a chunk of one tap whose step is the
+// launch's own "T", so the kernel takes the x_final pointer, here `state`, and no tape is read
+int launch_tap_loss_state(const gnca_step_desc* d, const gnca_rollout_taps* taps, int r, const float* state,
+                          float* losses, int32_t* alive_count, hipStream_t st) {
+  TapLossArgs a;
+  a.m = taps->masked;   // (B, H, W are the desc's: taps_ok)
+  a.T = taps->steps[r];
+  a.tape = nullptr;
+  a.slot = 0;
+  a.sstride = (size_t)d->C * d->H * d->W;
+  a.x_final = state;
+  a.tgt = taps->target; a.tbs = (long)taps->target_bstride;
+  a.losses = losses; a.alive_count = alive_count;
+  TapChunk ch;
+  ch.first = r;
+  for (int j = 0; j < GNCA_TAP_CHUNK; ++j) ch.step[j] = j == 0 ? a.T : 0;
+  const dim3 grid((unsigned)d->B, 1u), block(kThreads);
+  if (taps->kind == GNCA_TAP_MASKED) hipLaunchKernelGGL(gnca_tap_loss<GNCA_TAP_MASKED>, grid, block, 0, st, a, ch);
+  else hipLaunchKernelGGL(gnca_tap_loss<GNCA_TAP_PREMULT>, grid, block, 0, st, a, ch);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
 }  // namespace gnca
 
 extern "C" int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
@@ -1381,6 +1405,8 @@ extern "C" int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_roll
                                      const float* x_final, float* losses, int32_t* alive_count) {
   if (!taps_ok(desc, sched, taps) || !x_final || !losses) return GNCA_ERR_INVALID;
   if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  // a checkpointed tape holds the anchors only: gnca_rollout_fwd_taps writes the losses instead
+  if (sched->flags & GNCA_SCHED_CHECKPOINT) return GNCA_ERR_INVALID;
   TapeLayout L;
   if (!tape_layout(desc, sched, &L)) return GNCA_ERR_INVALID;
   if (!tape) return GNCA_ERR_INVALID;

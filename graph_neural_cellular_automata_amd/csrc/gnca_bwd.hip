@@ -2393,9 +2393,15 @@ static int step_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, cons
 // message-off steps, masked and full steps plan different BB instances and grids; the column layout
 // depends on C and the hidden width alone, so one block serves them all) and that many rows are reduced:
 // the rows a smaller grid leaves alone stay zero.
+// With GNCA_SCHED_CHECKPOINT the segment area follows, m = min(k, T):
+//   [... | m-1 states | n_ws forward workspaces],  n_ws = m-1, or min(m-1, 1) with GNCA_SCHED_RECOMPUTE
+// State i of the area is S_{jk+1+i} of the segment j in hand (S_jk is anchor j on the tape), written by
+// the re-run forward of step jk+i into workspace i (RECOMPUTE: workspace 0 for every step).  The
+// segment's last step is not re-run, so m-1 of each; bytes grows by exactly seg_bytes + segws_bytes.
 struct RollBwdLayout {
   TapeLayout T;
   size_t off_g[2], off_pb, off_pa, off_pq, off_step, step_bytes, pb_bytes, pa_bytes, pq_bytes, bytes;
+  size_t off_seg, seg_bytes, off_segws, segws_bytes;
   long pb_rows;
   int npart, nbands, nq;
   int o_w1, o_b1, o_w2, o_wm, o_bm;
@@ -2450,6 +2456,11 @@ static bool roll_bwd_layout(const gnca_step_desc* desc, const gnca_rollout_sched
   R->off_pa = o; o += R->pa_bytes;
   R->off_pq = o; o += R->pq_bytes;
   R->off_step = o; o += R->step_bytes;
+  const size_t m1 = R->T.k > 0 ? (size_t)std::max(std::min(R->T.k, s->steps) - 1, 0) : 0;
+  R->seg_bytes = m1 * R->T.state;
+  R->segws_bytes = ((s->flags & GNCA_SCHED_RECOMPUTE) ? std::min<size_t>(m1, 1) : m1) * R->T.fwd_ws;
+  R->off_seg = o; o += R->seg_bytes;
+  R->off_segws = o; o += R->segws_bytes;
   R->bytes = o;
   return true;
 }
@@ -2542,15 +2553,20 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
     return rc;
   }
   const bool recompute = (sched->flags & GNCA_SCHED_RECOMPUTE) != 0;
+  const int k = T > 0 ? R.T.k : 0;         // checkpointed: segments of k steps, anchors on the tape
   const float* g = gy;
   int t_first = T - 1;                     // the first step whose backward runs
   int r = tb ? tb->taps->n - 1 : -1;       // the next tap, walking the list backwards
+  int tl_wait = 0;                         // checkpointed: the first injection waits for its segment's re-run
   if (tb) {
     // A tap at T, or no gy: the first cotangent buffer is written whole (gy + the tap's gradient, or
     // the gradient and zeros), so gy is never modified and nothing is copied.  Without gy the steps
     // after the last tap are not run: their cotangent is zero.
     const int tl = tb->taps->steps[r];
-    if (tl == T || !gy) {
+    if (k > 0 && tl != T && !gy) {
+      tl_wait = tl;
+      t_first = tl - 1;
+    } else if (tl == T || !gy) {
       const float* state = tl == T ? tb->x_final : reinterpret_cast<const float*>(tp + (size_t)tl * R.T.slot);
       float* first = gb[tl & 1];
       rc = launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count,
@@ -2561,21 +2577,80 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
       --r;
     }
   }
-  for (int t = t_first; t >= 0; --t) {
-    gnca_step_desc sd;
-    sched_step_desc(desc, sched, t, &sd);
-    const float* xt = reinterpret_cast<const float*>(tp + (size_t)t * R.T.slot);
-    const void* saved = recompute ? nullptr : static_cast<const void*>(tp + (size_t)t * R.T.slot + R.T.state);
-    float* out = t == 0 ? gx : gb[t & 1];
-    rc = step_bwd_impl(&sd, w, xt, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), g, out,
-                       nullptr, saved, wsb + R.off_step, R.step_bytes, stream, &acc);
-    if (rc != GNCA_OK) return rc;
-    g = out;
-    if (r >= 0 && tb->taps->steps[r] == t) {   // dL/dS_t is complete but for this tap (t >= 1: out is gb[t & 1])
-      rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out, false,
-                             st);
+  if (k == 0) {
+    for (int t = t_first; t >= 0; --t) {
+      gnca_step_desc sd;
+      sched_step_desc(desc, sched, t, &sd);
+      const float* xt = reinterpret_cast<const float*>(tp + (size_t)t * R.T.slot);
+      const void* saved = recompute ? nullptr : static_cast<const void*>(tp + (size_t)t * R.T.slot + R.T.state);
+      float* out = t == 0 ? gx : gb[t & 1];
+      rc = step_bwd_impl(&sd, w, xt, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), g,
+                         out, nullptr, saved, wsb + R.off_step, R.step_bytes, stream, &acc);
       if (rc != GNCA_OK) return rc;
-      --r;
+      g = out;
+      if (r >= 0 && tb->taps->steps[r] == t) {   // dL/dS_t is complete but for this tap (t >= 1: out is gb[t & 1])
+        rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out,
+                               false, st);
+        if (rc != GNCA_OK) return rc;
+        --r;
+      }
+    }
+  } else {
+    // Segments j = t_first / k .. 0 (those wholly after the last tap of a taps-only call are skipped).
+    // Segment j: steps t0 = jk .. t1.  S_t0 is anchor j; the forward of steps t0 .. t1-1 is re-run with
+    // the forward's own calls and leaves S_{t0+1+i} in state i of the segment area.  Step t1's forward
+    // is not needed (its output is the next anchor, x_final, or unused): its backward recomputes K0 / K1.
+    const int m1 = std::max(std::min(k, T) - 1, 0);   // states (and step indices) of the segment area
+    auto seg_state = [&](int i) { return reinterpret_cast<float*>(wsb + R.off_seg + (size_t)i * R.T.state); };
+    auto seg_ws = [&](int i) { return wsb + R.off_segws + (recompute ? 0 : (size_t)i * R.T.fwd_ws); };
+    for (int j = t_first / k; j >= 0 && t_first >= 0; --j) {
+      const int t0 = j * k, t1 = std::min(std::min(t0 + k, T) - 1, t_first);
+      auto state_of = [&](int t) {
+        return t == t0 ? reinterpret_cast<const float*>(tp + (size_t)j * R.T.slot)
+                       : static_cast<const float*>(seg_state(t - t0 - 1));
+      };
+      // a waiting first tap inside this segment (tl_wait = t1 + 1, not an anchor) needs S_{t1+1} too
+      const bool wait_here = tl_wait > 0 && tl_wait % k != 0;
+      const int nfwd = t1 - t0 + (wait_here ? 1 : 0);
+      if (nfwd > m1) return GNCA_ERR_INVALID;   // (cannot happen: t1 - t0 <= m1, and < m1 when waiting)
+      for (int i = 0; i < nfwd; ++i) {
+        const int t = t0 + i;
+        gnca_step_desc sd;
+        sched_step_desc(desc, sched, t, &sd);
+        rc = gnca_step_masked_phases(&sd, w, state_of(t), seg_state(i), sched_step_fire(desc, sched, t),
+                                     sched_step_active(desc, sched, t, masks), seg_ws(i), R.T.fwd_ws, stream,
+                                     GNCA_PHASE_ALL);
+        if (rc != GNCA_OK) return rc;
+      }
+      if (tl_wait > 0) {   // (the first segment walked)
+        const float* state = wait_here ? static_cast<const float*>(seg_state(tl_wait - t0 - 1))
+                                       : reinterpret_cast<const float*>(tp + (size_t)(tl_wait / k) * R.T.slot);
+        float* first = gb[tl_wait & 1];
+        rc = launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, first,
+                               true, st);
+        if (rc != GNCA_OK) return rc;
+        g = first;
+        --r;
+        tl_wait = 0;
+      }
+      for (int t = t1; t >= t0; --t) {
+        gnca_step_desc sd;
+        sched_step_desc(desc, sched, t, &sd);
+        const float* xt = state_of(t);
+        const void* saved = (recompute || t - t0 >= nfwd) ? nullptr : static_cast<const void*>(seg_ws(t - t0));
+        float* out = t == 0 ? gx : gb[t & 1];
+        rc = step_bwd_impl(&sd, w, xt, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), g,
+                           out, nullptr, saved, wsb + R.off_step, R.step_bytes, stream, &acc);
+        if (rc != GNCA_OK) return rc;
+        g = out;
+        if (r >= 0 && tb->taps->steps[r] == t) {
+          rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out,
+                                 false, st);
+          if (rc != GNCA_OK) return rc;
+          --r;
+        }
+      }
+      t_first = t0 - 1;
     }
   }
   if (!grads) return GNCA_OK;

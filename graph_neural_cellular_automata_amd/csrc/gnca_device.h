@@ -299,6 +299,7 @@ inline bool sched_ok(const gnca_step_desc* d, const gnca_rollout_sched* s) {
   if (!d || !s || s->steps < 0 || s->full_steps < 0) return false;
   if (d->num_offsets < 0 || d->num_offsets > GNCA_MAX_OFFSETS) return false;
   if ((d->flags & GNCA_GRAPH) && d->num_offsets > 0 && s->steps > 0 && !s->offsets) return false;
+  if ((s->flags & GNCA_SCHED_CHECKPOINT) && s->ckpt_every < 1) return false;   // (read only with the flag)
   return true;
 }
 
@@ -334,8 +335,11 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // The tape: slot t = [state S_t | the step's forward workspace (absent with GNCA_SCHED_RECOMPUTE)].
 // fwd_ws: the largest forward workspace of the schedule's steps (plans differ between message-on
 // and message-off steps and with the offsets' reach).
+// With GNCA_SCHED_CHECKPOINT (k = ckpt_every > 0 here, else 0) the tape is the anchors alone:
+// slot j = [state S_jk], j < anchors = ceil(T / k), so slot == state and bytes == anchors * state.
 struct TapeLayout {
   size_t state, fwd_ws, slot, bytes, masks;
+  int k, anchors;
 };
 bool tape_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, TapeLayout* out);
 
@@ -344,6 +348,11 @@ int launch_nsteps_masks(const int32_t* nsteps, int B, int T, int full_steps, uin
 
 // The tap list of gnca_rollout_tap_loss / gnca_rollout_bwd_taps, validated (gnca_aux.hip)
 bool taps_ok(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps);
+
+// losses[r][b] (and, for tap 0 of the masked kind, alive_count) of one tap from its state's address
+// [B,C,H,W]: gnca_rollout_tap_loss's kernel and workgroups, one launch (gnca_aux.hip)
+int launch_tap_loss_state(const gnca_step_desc* d, const gnca_rollout_taps* taps, int r, const float* state,
+                          float* losses, int32_t* alive_count, hipStream_t st);
 
 // One tap's loss gradient into the backward's running cotangent (gnca_tap_inject, gnca_aux.hip).
 // state: S_t [B,C,H,W]; gl: g_losses[r] [B].  full == false: dst[b, c<4] += v in place (the other

@@ -2760,8 +2760,15 @@ bool tape_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, TapeLayou
   }
   out->state = align256((size_t)d->B * d->C * d->H * d->W * sizeof(float));
   out->fwd_ws = align256(m);
-  out->slot = out->state + ((s->flags & GNCA_SCHED_RECOMPUTE) ? 0 : out->fwd_ws);
-  out->bytes = (size_t)s->steps * out->slot;
+  out->k = (s->flags & GNCA_SCHED_CHECKPOINT) ? s->ckpt_every : 0;
+  out->anchors = out->k > 0 ? (int)(((long)s->steps + out->k - 1) / out->k) : 0;
+  if (out->k > 0) {   // the anchors S_0, S_k, ...: states alone, whatever GNCA_SCHED_RECOMPUTE says
+    out->slot = out->state;
+    out->bytes = (size_t)out->anchors * out->state;
+  } else {
+    out->slot = out->state + ((s->flags & GNCA_SCHED_RECOMPUTE) ? 0 : out->fwd_ws);
+    out->bytes = (size_t)s->steps * out->slot;
+  }
   out->masks = align256((size_t)std::max(s->steps, 1) * d->B);
   return true;
 }
@@ -2781,9 +2788,20 @@ size_t gnca_rollout_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_r
   return tape_layout(desc, sched, &L) ? L.masks + L.fwd_ws + 2 * L.state : 0;
 }
 
-int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
-                         const float* x, float* x_final, void* tape, size_t tape_bytes, void* ws,
-                         size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+// the taps of gnca_rollout_fwd_taps (validated by the caller: taps_ok, losses, alive_count)
+struct TapsFwd {
+  const gnca_rollout_taps* taps;
+  float* losses;
+  int32_t* alive_count;
+};
+
+// The body of gnca_rollout_fwd_f32 (tf == nullptr: exactly its launches) and of gnca_rollout_fwd_taps
+// (tf != nullptr: a tap's losses are written right after its step wrote the state).
+static int rollout_fwd_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                            const float* x, float* x_final, void* tape, size_t tape_bytes, void* ws,
+                            size_t ws_bytes, void* stream, const TapsFwd* tf) {
   if (!desc || !w || !sched || !x || !x_final || x == x_final) return GNCA_ERR_INVALID;
   TapeLayout L;
   if (!tape_layout(desc, sched, &L)) return GNCA_ERR_INVALID;
@@ -2809,23 +2827,53 @@ int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w, cons
   }
   if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, desc->B, T, sched->full_steps, masks, st)) != GNCA_OK)
     return rc;
-  const bool slot_ws = tape && !(sched->flags & GNCA_SCHED_RECOMPUTE);
+  // checkpointed: only S_k, S_2k, ... go to the tape (slot j = S_jk), the states between them
+  // alternate between the no-tape form's two buffers and every step uses the workspace in `ws`
+  const int k = tape ? L.k : 0;
+  const bool slot_ws = tape && k == 0 && !(sched->flags & GNCA_SCHED_RECOMPUTE);
   const float* cur = x;
   if (tape) {   // the tape stands alone: slot 0 keeps its own copy of x
     if (hipMemcpyAsync(tp, x, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
     cur = reinterpret_cast<const float*>(tp);
   }
+  int r = 0;   // the next tap
   for (int t = 0; t < T; ++t) {
     gnca_step_desc sd;
     sched_step_desc(desc, sched, t, &sd);
-    float* nxt = t == T - 1 ? x_final : tape ? reinterpret_cast<float*>(tp + (size_t)(t + 1) * L.slot) : pp[t & 1];
+    float* nxt;
+    if (t == T - 1) nxt = x_final;
+    else if (!tape) nxt = pp[t & 1];
+    else if (k == 0) nxt = reinterpret_cast<float*>(tp + (size_t)(t + 1) * L.slot);
+    else nxt = (t + 1) % k == 0 ? reinterpret_cast<float*>(tp + (size_t)((t + 1) / k) * L.slot) : pp[t & 1];
     void* sws = slot_ws ? static_cast<void*>(tp + (size_t)t * L.slot + L.state) : static_cast<void*>(step_ws);
     rc = step_impl(&sd, w, cur, nxt, sched_step_fire(desc, sched, t), nullptr, sws, L.fwd_ws, st, GNCA_PHASE_ALL,
                    sched_step_active(desc, sched, t, masks));
     if (rc != GNCA_OK) return rc;
     cur = nxt;
+    if (tf && r < tf->taps->n && tf->taps->steps[r] == t + 1) {
+      rc = launch_tap_loss_state(desc, tf->taps, r, nxt, tf->losses, tf->alive_count, st);
+      if (rc != GNCA_OK) return rc;
+      ++r;
+    }
   }
   return GNCA_OK;
+}
+
+extern "C" {
+
+int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const float* x, float* x_final, void* tape, size_t tape_bytes, void* ws,
+                         size_t ws_bytes, void* stream) {
+  return rollout_fwd_impl(desc, w, sched, x, x_final, tape, tape_bytes, ws, ws_bytes, stream, nullptr);
+}
+
+int gnca_rollout_fwd_taps(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                          const gnca_rollout_taps* taps, const float* x, float* x_final, void* tape,
+                          size_t tape_bytes, float* losses, int32_t* alive_count, void* ws, size_t ws_bytes) {
+  if (!taps_ok(desc, sched, taps) || !losses) return GNCA_ERR_INVALID;
+  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  const TapsFwd tf = {taps, losses, alive_count};
+  return rollout_fwd_impl(desc, w, sched, x, x_final, tape, tape_bytes, ws, ws_bytes, taps->stream, &tf);
 }
 
 }  // extern "C"

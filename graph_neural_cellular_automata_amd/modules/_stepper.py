@@ -292,7 +292,14 @@ class _RolloutFn(torch.autograd.Function):
 def _rollout_desc(model: nn.Module, x, steps: int, graph, hidden_only: bool, sched):
     """(desc, weights, keep, tensors) of a rollout of ``sched`` on ``x``: the shared front of
     ``run_rollout`` and ``run_trace``."""
-    B, C, H, W = x.shape
+    desc, tensors = _rollout_desc_host(model, tuple(x.shape), steps, graph, hidden_only, sched)
+    w, keep = S.make_weights(tensors)
+    return desc, w, keep, tensors
+
+
+def _rollout_desc_host(model: nn.Module, shape, steps: int, graph, hidden_only: bool, sched):
+    """(desc, tensors): the descriptor alone, from the state's shape (no device pointer is taken)."""
+    B, C, H, W = shape
     flags, eps = _check_norm(model)
     tensors = _step_tensors(model, graph)
     d_model = 1
@@ -316,8 +323,7 @@ def _rollout_desc(model: nn.Module, x, steps: int, graph, hidden_only: bool, sch
         desc.num_offsets = min(graph.num_neighbors, len(graph.offsets))
     desc.rng_seed = sched.seed & 0xFFFFFFFFFFFFFFFF
     desc.sample_base = sched.sample_base
-    w, keep = S.make_weights(tensors)
-    return desc, w, keep, tensors
+    return desc, tensors
 
 
 def _check_norm(model: nn.Module):
@@ -334,16 +340,18 @@ def _check_norm(model: nn.Module):
 
 def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
                 message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0, offsets=None,
-                recompute=False):
+                recompute=False, checkpoint_every=None):
     """``steps`` CA steps in one native call (and, with grad, one autograd node): the shared body of
     ``NeuralCA.rollout`` / ``NeuralCAGraph.rollout``."""
+    S.checkpoint_interval(checkpoint_every, steps if isinstance(steps, int) else 0)   # (pure Python, first)
     x = S.check_state(x, model.n_channels)
     B, C, H, W = x.shape
     _check_norm(model)   # (before the schedule draws its offsets)
     sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
                              message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                              sample_base=sample_base, offsets=offsets,
-                             sample_offsets=None if graph is None else graph.sample_offsets, recompute=recompute)
+                             sample_offsets=None if graph is None else graph.sample_offsets, recompute=recompute,
+                             checkpoint_every=checkpoint_every)
     desc, w, keep, tensors = _rollout_desc(model, x, steps, graph, hidden_only, sched)
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors.values())):
         core, gpack = param_packs(model, tensors)
@@ -357,17 +365,55 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
     return out
 
 
+def run_rollout_memory(model: nn.Module, x_or_shape, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
+                       message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0,
+                       offsets=None, recompute=False, checkpoint_every=None) -> dict:
+    """The shared body of ``rollout_memory``: the schedule ``rollout()`` would build for these
+    arguments, asked for its sizes.  Host-only; Python's and torch's RNG states are put back."""
+    import random
+    if isinstance(x_or_shape, torch.Tensor):
+        shape, device = tuple(x_or_shape.shape), x_or_shape.device
+    else:
+        shape = tuple(int(v) for v in x_or_shape)
+        given = nsteps if nsteps is not None else fire
+        device = given.device if isinstance(given, torch.Tensor) else torch.device("cpu")
+    if len(shape) != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {shape}")
+    if shape[1] != model.n_channels:
+        raise ValueError(f"state has {shape[1]} channels, model expects {model.n_channels}")
+    B, C, H, W = shape
+    _check_norm(model)
+    py_state, torch_state = random.getstate(), torch.get_rng_state()
+    try:
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                                 seed=seed, sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets,
+                                 recompute=recompute, checkpoint_every=checkpoint_every)
+    finally:
+        random.setstate(py_state)
+        torch.set_rng_state(torch_state)
+    desc, _ = _rollout_desc_host(model, shape, steps, graph, hidden_only, sched)
+    return S.RolloutCall(desc, sched).memory()
+
+
 class _RolloutObjectiveFn(torch.autograd.Function):
     """A whole rollout AND the per-sample losses of its tapped states as ONE autograd node with two
     outputs: ``gnca_rollout_fwd_f32`` with a tape and ``gnca_rollout_tap_loss`` on that tape forward,
     ``gnca_rollout_bwd_taps`` backward.  Either output's cotangent may be absent (no zero tensor is
-    made for it); the parameter gradients leave through the packs as in ``_RolloutFn``."""
+    made for it); the parameter gradients leave through the packs as in ``_RolloutFn``.  With
+    ``checkpoint_every`` the forward is ``gnca_rollout_fwd_taps``: the losses are written as the states are
+    produced, since the checkpointed tape keeps only every k-th of them."""
 
     @staticmethod
     def forward(ctx, x, call, taps, weights, keep, core, graph, tok_core, tok_graph, tensors=None):
         ctx.set_materialize_grads(False)
-        out, tape = call.forward(weights, x, want_tape=True)
-        losses, alive = call.tap_losses(taps, tape, out)
+        if call.schedule.checkpoint_every is not None:
+            # most tapped states never reach a checkpointed tape: the forward writes their losses
+            out, tape, losses, alive = call.forward_taps(weights, taps, x, want_tape=True)
+        else:
+            out, tape = call.forward(weights, x, want_tape=True)
+            losses, alive = call.tap_losses(taps, tape, out)
         ctx.call, ctx.taps, ctx.weights, ctx.keep, ctx.tape, ctx.alive = call, taps, weights, keep, tape, alive
         ctx.packs = (core, graph)
         ctx.save_for_backward(out)   # (the state of a tap at the last step: it is not on the tape)
@@ -424,7 +470,8 @@ class RolloutObjective:
 def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target, graph, hidden_only: bool, *,
                           every=1, record=None, loss="premult", alpha_thr=0.2, lam_area=5e-5, lam_bg_alpha=0.0,
                           lam_bg_rgb=0.0, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0, fire=None,
-                          seed=None, sample_base=0, offsets=None, recompute=False) -> RolloutObjective:
+                          seed=None, sample_base=0, offsets=None, recompute=False,
+                          checkpoint_every=None) -> RolloutObjective:
     """The shared body of ``NeuralCA.rollout_objective`` / ``NeuralCAGraph.rollout_objective``."""
     from .. import loss as LS
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
@@ -446,6 +493,7 @@ def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target,
     rec = S.expand_record(steps, every, record)
     if not rec:
         raise ValueError("record is empty: a rollout objective needs at least one tapped step")
+    S.checkpoint_interval(checkpoint_every, steps)
     x = S.check_state(x, model.n_channels)   # (channels, device, dtype: before the schedule draws its offsets)
     tensors = _step_tensors(model, graph)
     grad = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors.values()))
@@ -454,7 +502,7 @@ def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target,
                              message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                              sample_base=sample_base, offsets=offsets,
                              sample_offsets=None if graph is None else graph.sample_offsets,
-                             recompute=recompute if grad else True)
+                             recompute=recompute if grad else True, checkpoint_every=checkpoint_every)
     desc, w, keep, tensors = _rollout_desc(model, x, steps, graph, hidden_only, sched)
     tgt = target.detach().to(x.device, torch.float32)
     tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
@@ -464,6 +512,8 @@ def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target,
         tc = core.token if core is not None else None
         tg = gpack.token if gpack is not None else None
         out, losses = _RolloutObjectiveFn.apply(x, call, taps, w, keep, core, gpack, tc, tg, tensors)
+    elif checkpoint_every is not None:
+        out, _, losses, _ = call.forward_taps(w, taps, x, want_tape=False)   # (no tape at all)
     else:
         out, tape = call.forward(w, x, want_tape=True)
         losses, _ = call.tap_losses(taps, tape, out)

@@ -3,7 +3,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import RolloutObjective, TraceResult, run_rollout, run_rollout_objective, run_step, run_trace
+from ._stepper import (RolloutObjective, TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+                       run_step, run_trace)
 from .perception import FixedSobelPerception
 
 
@@ -37,17 +38,28 @@ class NeuralCA(nn.Module):
         return out
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
-                fire=None, seed=None, sample_base: int = 0, recompute: bool = False) -> torch.Tensor:
+                fire=None, seed=None, sample_base: int = 0, recompute: bool = False,
+                checkpoint_every=None) -> torch.Tensor:
         """``steps`` CA steps in one native call, one autograd node with grad enabled: see
         ``NeuralCAGraph.rollout`` (no ``message_gain`` / ``offsets`` here)."""
         return run_rollout(self, x, steps, None, False, fire_rate=fire_rate, nsteps=nsteps, min_steps=min_steps,
-                           fire=fire, seed=seed, sample_base=sample_base, recompute=recompute)
+                           fire=fire, seed=seed, sample_base=sample_base, recompute=recompute,
+                           checkpoint_every=checkpoint_every)
+
+    def rollout_memory(self, x_or_shape, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
+                       fire=None, seed=None, sample_base: int = 0, recompute: bool = False,
+                       checkpoint_every=None) -> dict:
+        """Bytes ``rollout()`` with these arguments needs on the device: see
+        ``NeuralCAGraph.rollout_memory``."""
+        return run_rollout_memory(self, x_or_shape, steps, None, False, fire_rate=fire_rate, nsteps=nsteps,
+                                  min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
+                                  recompute=recompute, checkpoint_every=checkpoint_every)
 
     def rollout_objective(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, every: int = 1, record=None,
                           loss: str = "premult", alpha_thr: float = 0.2, lam_area: float = 5e-5,
                           lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0, fire_rate=1.0, nsteps=None,
                           min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
-                          recompute: bool = False) -> RolloutObjective:
+                          recompute: bool = False, checkpoint_every=None) -> RolloutObjective:
         """``rollout()`` that also returns per-sample losses at intermediate steps, as one autograd node:
         see ``NeuralCAGraph.rollout_objective`` (no ``message_gain`` / ``offsets`` here).  Under
         ``no_grad`` it still returns ``x_final`` and ``losses`` (a states-only tape, freed at once); the
@@ -56,7 +68,7 @@ class NeuralCA(nn.Module):
                                      alpha_thr=alpha_thr, lam_area=lam_area, lam_bg_alpha=lam_bg_alpha,
                                      lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate, nsteps=nsteps,
                                      min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
-                                     recompute=recompute)
+                                     recompute=recompute, checkpoint_every=checkpoint_every)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

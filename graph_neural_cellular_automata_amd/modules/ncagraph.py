@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import RolloutObjective, TraceResult, run_rollout, run_rollout_objective, run_step, run_trace
+from ._stepper import (RolloutObjective, TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+                       run_step, run_trace)
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -72,7 +73,7 @@ class NeuralCAGraph(nn.Module):
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
                 min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,
-                recompute: bool = False) -> torch.Tensor:
+                recompute: bool = False, checkpoint_every=None) -> torch.Tensor:
         """``steps`` CA steps in one native call (extension, not in the reference); with grad enabled
         the whole rollout is ONE autograd node whose backward walks a device-side tape and reduces
         the weight gradients once per rollout.
@@ -87,19 +88,41 @@ class NeuralCAGraph(nn.Module):
         below 1 uses the counter-based hash masks of ``seed`` (``seed=None`` draws one integer from
         torch's default CPU generator) -- NOT the ``torch.rand`` stream ``forward`` draws from.
         ``recompute=True`` halves the tape (the backward recomputes each step's update field).
+        ``checkpoint_every=k`` (an int >= 1, or ``"auto"`` = ``ceil(sqrt(steps))``) bounds it: the tape
+        keeps every k-th state only and the backward re-runs the forward one segment of k steps at a
+        time, so a 400-step rollout keeps 20 + 19 states instead of 400 at the price of one more
+        forward.  ``x.grad`` and every parameter gradient are bitwise those of the plain tape; it
+        composes with every other keyword (``rollout_memory`` gives the sizes).  Ignored under
+        ``no_grad``, which records no tape.
         Under ``no_grad`` a uniform schedule (one rate, one gain, no ``nsteps``, hash or no fire)
         runs the large-batch rollout pipeline (``gnca_rollout_ex_f32``).  ``return_attention`` is
         not supported here: ``trace()`` records frames and attention maps."""
         return run_rollout(self, x, steps, self.graph, self.hidden_only, fire_rate=fire_rate,
                            message_gain=self.message_gain if message_gain is None else message_gain,
                            nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
-                           offsets=offsets, recompute=recompute)
+                           offsets=offsets, recompute=recompute, checkpoint_every=checkpoint_every)
+
+    def rollout_memory(self, x_or_shape, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
+                       min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,
+                       recompute: bool = False, checkpoint_every=None) -> dict:
+        """Bytes ``rollout()`` with these arguments needs on the device, as ``{"tape",
+        "forward_workspace", "backward_workspace"}``, from the library's host-only size queries: no
+        GPU is touched, so it also runs on a machine without one.  ``x_or_shape``: the state or its
+        (B, C, H, W).  The schedule is built as ``rollout()`` builds it (``offsets=None`` draws them,
+        which can move the workspaces by the offsets' reach), and Python's ``random`` and torch's CPU
+        generator are left as they were found.  The tape and the backward workspace live from the
+        forward to the end of the backward, the forward workspace during the forward only."""
+        return run_rollout_memory(self, x_or_shape, steps, self.graph, self.hidden_only, fire_rate=fire_rate,
+                                  message_gain=self.message_gain if message_gain is None else message_gain,
+                                  nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                  sample_base=sample_base, offsets=offsets, recompute=recompute,
+                                  checkpoint_every=checkpoint_every)
 
     def rollout_objective(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, every: int = 1, record=None,
                           loss: str = "premult", alpha_thr: float = 0.2, lam_area: float = 5e-5,
                           lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0, fire_rate=1.0, message_gain=None,
                           nsteps=None, min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
-                          offsets=None, recompute: bool = False) -> RolloutObjective:
+                          offsets=None, recompute: bool = False, checkpoint_every=None) -> RolloutObjective:
         """``rollout()`` that also returns per-sample losses at intermediate steps, as ONE autograd node
         (extension, not in the reference): the trainers' supervision of several steps of one rollout
         without a chain of ``rollout()`` + loss nodes.
@@ -120,15 +143,20 @@ class NeuralCAGraph(nn.Module):
         ``nsteps[b]`` below a tapped step contributes the loss of its frozen state.  A second backward
         raises, as for ``rollout()``.
 
+        ``checkpoint_every`` is ``rollout()``'s: the forward then writes each tap's loss as its state is
+        produced (``gnca_rollout_fwd_taps``), since a checkpointed tape holds few of the tapped states;
+        losses and gradients are bitwise those of the plain tape.
+
         Under ``no_grad``, or when nothing requires grad, ``x_final`` and ``losses`` are still returned
-        (a states-only tape is recorded and freed); that is not the tuned no-grad path, which stays
-        ``trace(..., target=)``."""
+        (a states-only tape is recorded and freed; with ``checkpoint_every`` no tape at all); that is
+        not the tuned no-grad path, which stays ``trace(..., target=)``."""
         return run_rollout_objective(self, x, steps, target, self.graph, self.hidden_only, every=every,
                                      record=record, loss=loss, alpha_thr=alpha_thr, lam_area=lam_area,
                                      lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate,
                                      message_gain=self.message_gain if message_gain is None else message_gain,
                                      nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                     sample_base=sample_base, offsets=offsets, recompute=recompute)
+                                     sample_base=sample_base, offsets=offsets, recompute=recompute,
+                                     checkpoint_every=checkpoint_every)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

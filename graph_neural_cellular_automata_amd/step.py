@@ -5,6 +5,7 @@ Everything here is plumbing around ``libgnca.so``; the arithmetic is in the HIP 
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -355,7 +356,7 @@ class Schedule:
     the caller's device tensors; ``RolloutCall`` turns it into the C struct."""
 
     __slots__ = ("steps", "full_steps", "recompute", "offsets", "k", "fire_rates", "gains", "nsteps",
-                 "fire", "fire_mode", "seed", "sample_base")
+                 "fire", "fire_mode", "seed", "sample_base", "checkpoint_every")
 
     @property
     def uniform(self) -> bool:
@@ -377,9 +378,24 @@ def _per_step(value, steps: int, name: str) -> list:
     return vals
 
 
+def checkpoint_interval(checkpoint_every, steps: int):
+    """``checkpoint_every`` validated: None (no checkpointing), an int >= 1, or ``"auto"`` =
+    ``ceil(sqrt(steps))``, which minimises the ``steps / k`` anchors plus the ``k`` segment states."""
+    if checkpoint_every is None:
+        return None
+    if isinstance(checkpoint_every, str):
+        if checkpoint_every != "auto":
+            raise ValueError(f"checkpoint_every must be None, an int >= 1 or 'auto', got {checkpoint_every!r}")
+        k = math.isqrt(max(int(steps), 1))
+        return max(k if k * k >= steps else k + 1, 1)
+    if isinstance(checkpoint_every, bool) or not isinstance(checkpoint_every, int) or checkpoint_every < 1:
+        raise ValueError(f"checkpoint_every must be None, an int >= 1 or 'auto', got {checkpoint_every!r}")
+    return checkpoint_every
+
+
 def build_schedule(*, steps, B, H, W, device, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0,
                    fire=None, seed=None, sample_base=0, offsets=None, sample_offsets=None,
-                   recompute=False) -> Schedule:
+                   recompute=False, checkpoint_every=None) -> Schedule:
     """Validate a rollout's arguments and build its schedule.  Pure Python: needs neither the
     library nor a GPU, and raises ``ValueError`` before anything is launched.
 
@@ -389,13 +405,17 @@ def build_schedule(*, steps, B, H, W, device, fire_rate=1.0, message_gain=None, 
     draws ``steps`` forward calls would make from Python's ``random``, message-off steps included).
     ``fire``: None (hash masks from ``seed`` when any rate is below 1; ``seed=None`` draws one
     integer from torch's default CPU generator) or a [steps,B,1,H,W] tensor on ``device``: float32
-    uniforms or uint8 / bool masks."""
+    uniforms or uint8 / bool masks.
+    ``checkpoint_every``: None, an int >= 1 or ``"auto"`` (``checkpoint_interval``): the tape keeps
+    every k-th state and the backward re-runs one segment of k steps at a time."""
     if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
         raise ValueError(f"steps must be a non-negative int, got {steps!r}")
     if isinstance(min_steps, bool) or not isinstance(min_steps, int) or min_steps < 0:
         raise ValueError(f"min_steps must be a non-negative int, got {min_steps!r}")
+    ckpt = checkpoint_interval(checkpoint_every, steps)   # (before any offset is drawn)
     device = torch.device(device)
     s = Schedule()
+    s.checkpoint_every = ckpt
     s.steps, s.full_steps, s.recompute = steps, min(min_steps, steps), bool(recompute)
     s.sample_base = int(sample_base)
     s.fire_rates = _per_step(fire_rate, steps, "fire_rate")
@@ -765,6 +785,9 @@ class RolloutCall:
         c = L.RolloutSched()
         c.steps, c.full_steps = T, sched.full_steps
         c.flags = L.SCHED_RECOMPUTE if sched.recompute else 0
+        if sched.checkpoint_every is not None:
+            c.flags |= L.SCHED_CHECKPOINT
+            c.ckpt_every = sched.checkpoint_every
         self._keep = []
         if sched.offsets is not None and k > 0 and T > 0:
             flat = [v for o in sched.offsets for pair in o for v in pair]
@@ -806,6 +829,36 @@ class RolloutCall:
                                       ws.data_ptr(), ws.numel(), stream_ptr(x.device))
         L.check(rc, "gnca_rollout_fwd_f32")
         return out, tape
+
+    def memory(self) -> dict:
+        """Bytes of the tape and of the two workspaces of this schedule, from the three host-only size
+        queries: no GPU is touched."""
+        lib = L.load()
+        return {"tape": lib.gnca_rollout_tape_bytes(ctypes.byref(self.desc), ctypes.byref(self.c)),
+                "forward_workspace": self._sizes(lib.gnca_rollout_fwd_workspace_bytes),
+                "backward_workspace": self._sizes(lib.gnca_rollout_bwd_workspace_bytes)}
+
+    def forward_taps(self, weights, taps: "RolloutTaps", x, want_tape: bool):
+        """(x_final, tape or None, losses [R,B], alive_count [B] or None): ``forward`` that also writes
+        the losses of the tapped states as they are produced (``gnca_rollout_fwd_taps``), so it serves
+        a checkpointed tape, which holds few of them, and the no-grad form, which has no tape."""
+        fn = _tap_entry("gnca_rollout_fwd_taps")
+        lib = L.load()
+        B, dev = self.desc.B, x.device
+        out = torch.empty_like(x)
+        tape = None
+        if want_tape:
+            nb = lib.gnca_rollout_tape_bytes(ctypes.byref(self.desc), ctypes.byref(self.c))
+            tape = torch.empty(max(nb, 256), dtype=torch.uint8, device=dev)
+        losses = torch.empty(taps.c.n, B, dtype=torch.float32, device=dev)
+        alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
+        ws = torch.empty(self._sizes(lib.gnca_rollout_fwd_workspace_bytes), dtype=torch.uint8, device=dev)
+        taps.c.stream = stream_ptr(dev)
+        rc = fn(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c), ctypes.byref(taps.c),
+                x.data_ptr(), out.data_ptr(), _ptr(tape), 0 if tape is None else tape.numel(), losses.data_ptr(),
+                _ptr(alive), ws.data_ptr(), ws.numel())
+        L.check(rc, "gnca_rollout_fwd_taps")
+        return out, tape, losses, alive
 
     def backward(self, weights, tape, gy, want: dict | None = None, out: dict | None = None):
         """(gx, {name: grad}) of the rollout that recorded ``tape`` (``want`` / ``out`` as in

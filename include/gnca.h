@@ -339,12 +339,35 @@ int gnca_step_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w, const f
  * and the sum of their gnca_step_bwd_f32 gradients.
  * -------------------------------------------------------------------------------------------*/
 #define GNCA_SCHED_RECOMPUTE (1u << 0)  /* tape keeps states only; the backward recomputes K0/K1 */
+/*
+ * Segment checkpointing, k = ckpt_every >= 1 (else GNCA_ERR_INVALID / size 0).  The tape keeps only
+ * the anchors S_0, S_k, S_2k, ...: A = ceil(T/k) states, each 256-byte aligned,
+ *   gnca_rollout_tape_bytes = A * align256(B*C*H*W*4)                         (0 for T = 0),
+ * and never a step workspace.  The forward writes the states between two anchors into the two
+ * buffers of its workspace (the no-tape form's; gnca_rollout_fwd_workspace_bytes does not grow).
+ * The backward takes the segments j = A-1 .. 0 in turn: it re-runs the forward of the segment's
+ * steps from anchor j into a segment area of its own workspace (the same step calls, descriptors,
+ * masks and fire inputs as the forward: the states are reproduced bit for bit), then walks the
+ * segment backwards as the plain backward does.  The last step of a segment is not re-run (nobody
+ * reads its output): its backward recomputes K0 / K1, as under GNCA_SCHED_RECOMPUTE.  With
+ * m = min(k, T),
+ *   gnca_rollout_bwd_workspace_bytes = (the plain schedule's) + (m-1) * state + n_ws * fwd_ws,
+ *   n_ws = m-1                    each re-run step keeps its forward workspace for its backward, or
+ *   n_ws = min(m-1, 1)            with GNCA_SCHED_RECOMPUTE: one workspace for the re-run steps,
+ * state = align256(B*C*H*W*4), fwd_ws = the schedule's largest step workspace (256-byte aligned).
+ * The accumulating rows are zeroed once, the steps' backwards arrive in the order T-1 .. 0 and each
+ * reduction runs once, so every gradient is bitwise that of the plain tape.  k = 1 keeps every
+ * state, k >= T only a copy of x.
+ */
+#define GNCA_SCHED_CHECKPOINT (1u << 1)
 
 typedef struct gnca_rollout_sched {
   int32_t steps;              /* T, host                                                        */
   int32_t full_steps;         /* steps t < full_steps run every sample whatever nsteps says     */
   uint32_t flags;
-  const int8_t* offsets;      /* host  [T][2*desc->num_offsets], as gnca_rollout_f32            */
+  int32_t ckpt_every;         /* k; read only with GNCA_SCHED_CHECKPOINT (it took the place of the
+                                 padding after flags: no offset and no size changed)            */
+  const int8_t* offsets;     /* host  [T][2*desc->num_offsets], as gnca_rollout_f32            */
   const float* fire_rate;     /* host  [T], NULL = desc->fire_rate for every step               */
   const float* message_gain;  /* host  [T], NULL = desc->message_gain                           */
   const int32_t* nsteps;      /* DEVICE [B]: sample b takes step t iff t < nsteps[b]; NULL = all */
@@ -366,6 +389,9 @@ size_t gnca_rollout_bwd_workspace_bytes(const gnca_step_desc* desc, const gnca_r
  * x).  tape: >= gnca_rollout_tape_bytes bytes, 256-B aligned, or NULL for the no-grad form of the
  * same schedule (the states then alternate between two buffers in `ws`).  nsteps is turned into
  * the per-step active masks on the device (one launch); it is never read on the host.
+ * With GNCA_SCHED_CHECKPOINT only the states S_k, S_2k, ... go to the tape (and a copy of x as
+ * S_0); the others alternate between the two buffers in `ws`, and every step uses the step
+ * workspace in `ws`.
  */
 int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
                          const gnca_rollout_sched* sched, const float* x, float* x_final, void* tape,
@@ -375,6 +401,8 @@ int gnca_rollout_fwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
  * BPTT through the rollout that wrote `tape` (same desc, weights and schedule, the tape unmodified
  * since): gy = dL/d x_final, gx = dL/dx (must not alias gy), grads written once (overwritten, in
  * the layouts of gnca_grads; a NULL pointer skips that gradient; grads itself may be NULL).
+ * With GNCA_SCHED_CHECKPOINT each segment's forward is re-run first (see the flag); x_final, gx and
+ * every gradient are bitwise those of the same schedule without the flag.
  */
 int gnca_rollout_bwd_f32(const gnca_step_desc* desc, const gnca_weights* w,
                          const gnca_rollout_sched* sched, const void* tape, size_t tape_bytes,
@@ -808,6 +836,17 @@ int gnca_loss_stability_bwd_f32(int32_t B, int32_t H, int32_t W, const float* pr
  * GNCA_ERR_INVALID before any launch: a null taps / steps / target, n < 1, steps not strictly
  * increasing or outside 1..sched->steps, an unknown kind, masked.B/H/W != desc's (either kind),
  * a missing alive_count (GNCA_TAP_MASKED), gy and g_losses both NULL, gx aliasing gy.
+ *
+ * Under GNCA_SCHED_CHECKPOINT most tapped states are not on the tape: gnca_rollout_tap_loss then
+ * returns GNCA_ERR_INVALID before any launch, and gnca_rollout_fwd_taps takes its place.  It is
+ * gnca_rollout_fwd_f32 (on taps->stream) that also writes losses[r][b] right after step steps[r]
+ * wrote its state, wherever that state lives: one launch of the same loss kernel per tap, given the
+ * state's address.  Valid for every schedule, with or without the flag, and with tape == NULL (the
+ * no-grad form); x_final and the losses are bitwise those of gnca_rollout_fwd_f32 followed by
+ * gnca_rollout_tap_loss.  It rejects what gnca_rollout_tap_loss rejects (a null or malformed tap
+ * list, a null losses, a missing alive_count).  gnca_rollout_bwd_taps under the flag injects a
+ * tap's gradient where it does without it, reading S_t from the segment area or the anchor; with
+ * gy == NULL the segments that lie wholly after the last tap are neither re-run nor walked.
  * -------------------------------------------------------------------------------------------*/
 #define GNCA_TAP_PREMULT 0
 #define GNCA_TAP_MASKED 1
@@ -827,6 +866,11 @@ int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_rollout_sched* 
                           const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes,
                           const float* x_final, float* losses /*[R][B]*/,
                           int32_t* alive_count /*[B], GNCA_TAP_MASKED only*/);
+int gnca_rollout_fwd_taps(const gnca_step_desc* desc, const gnca_weights* w,
+                          const gnca_rollout_sched* sched, const gnca_rollout_taps* taps,
+                          const float* x, float* x_final, void* tape /*or NULL*/, size_t tape_bytes,
+                          float* losses /*[R][B]*/, int32_t* alive_count /*[B], GNCA_TAP_MASKED only*/,
+                          void* ws /*gnca_rollout_fwd_workspace_bytes*/, size_t ws_bytes);
 int gnca_rollout_bwd_taps(const gnca_step_desc* desc, const gnca_weights* w,
                           const gnca_rollout_sched* sched, const gnca_rollout_taps* taps,
                           const void* tape, size_t tape_bytes, const float* x_final,

@@ -9,6 +9,11 @@ with their median, then the maximum gradient difference between the two paths.
 
     python tools/bench_rollout_bptt.py [--shape trainer|reference|both] [--repeats 5] [--window 1.0]
     python tools/bench_rollout_bptt.py --profile-backward    # three rollout iterations only (for a kernel trace)
+    python tools/bench_rollout_bptt.py --shape trainer --checkpoint-every auto [--recompute] [--steps 200 400]
+
+With ``--checkpoint-every`` the two alternating paths are ``model.rollout`` without and with
+``checkpoint_every`` (same windows, same schedule): the checkpointed backward re-runs the forward, so the
+yardstick printed beside it is the same run's plain backward plus plain forward.
 """
 from __future__ import annotations
 
@@ -70,8 +75,12 @@ def per_step_forward(model, x, ns, offs, gains):
     return s
 
 
-def rollout_forward(model, x, ns, offs, gains):
-    return model.rollout(x, HI, fire_rate=RATE, message_gain=gains, nsteps=ns, min_steps=LO, seed=SEED, offsets=offs)
+ROLLOUT_KW = {}   # --recompute
+
+
+def rollout_forward(model, x, ns, offs, gains, **kw):
+    return model.rollout(x, HI, fire_rate=RATE, message_gain=gains, nsteps=ns, min_steps=LO, seed=SEED, offsets=offs,
+                         **ROLLOUT_KW, **kw)
 
 
 def one_iteration(fwd, model, x, gy, ns, offs, gains):
@@ -88,10 +97,13 @@ def one_iteration(fwd, model, x, gy, ns, offs, gains):
     return t1 - t0, t2 - t1, leaf.grad, {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
 
 
-def bench(name, repeats, window, dev):
+def bench(name, repeats, window, dev, checkpoint_every=None):
     cfg = SHAPES[name]
     args = setup(cfg["B"], cfg["H"], dev)
     paths = {"per_step": per_step_forward, "rollout": rollout_forward}
+    if checkpoint_every is not None:
+        paths = {"per_step": rollout_forward,    # (the baseline's slot: the plain rollout)
+                 "rollout": lambda *a: rollout_forward(*a, checkpoint_every=checkpoint_every)}
     grads = {}
     for p, fn in paths.items():   # warm-up (plans, workspaces, allocator)
         for _ in range(2):
@@ -116,6 +128,16 @@ def bench(name, repeats, window, dev):
                       fwd_ms_median=round(statistics.median(r[0] for r in rows[p]), 3),
                       bwd_ms_median=round(statistics.median(r[1] for r in rows[p]), 3))
     res["max_grad_diff"] = {k: f"{diff[k]:.3e} (max|g| {scale[k]:.3e})" for k in diff}
+    if checkpoint_every is not None:
+        res["plain"], res["checkpointed"] = res.pop("per_step"), res.pop("rollout")
+        res["checkpoint_every"], res["recompute"] = checkpoint_every, bool(ROLLOUT_KW.get("recompute"))
+        res["memory_bytes"] = {
+            tag: args[0].rollout_memory(args[1], HI, fire_rate=RATE, message_gain=args[5], min_steps=LO, seed=SEED,
+                                        offsets=args[4], **ROLLOUT_KW, **kw)
+            for tag, kw in (("plain", {}), ("checkpointed", dict(checkpoint_every=checkpoint_every)))}
+        want = res["plain"]["bwd_ms_median"] + res["plain"]["fwd_ms_median"]
+        res["bwd_yardstick_ms"] = round(want, 3)     # plain backward + plain tape forward
+        res["bwd_over_yardstick"] = round(res["checkpointed"]["bwd_ms_median"] / want, 4)
     print(json.dumps(res), flush=True)
 
 
@@ -128,7 +150,22 @@ def main():
                     help="three rollout iterations at the trainer shape and nothing else (for a kernel trace)")
     ap.add_argument("--profile-per-step", action="store_true",
                     help="the same three iterations on the per-step path")
+    ap.add_argument("--checkpoint-every", default=None,
+                    help="an int >= 1 or 'auto': time model.rollout without and with checkpoint_every")
+    ap.add_argument("--recompute", action="store_true", help="recompute=True on both rollout paths")
+    ap.add_argument("--steps", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="per-sample rollout lengths are drawn from LO..HI (default 48 80)")
     a = ap.parse_args()
+    global LO, HI
+    if a.steps:
+        LO, HI = a.steps
+        if not 1 <= LO <= HI:
+            ap.error("--steps needs 1 <= LO <= HI")
+    if a.recompute:
+        ROLLOUT_KW["recompute"] = True
+    ck = a.checkpoint_every
+    if ck is not None and ck != "auto":
+        ck = int(ck)
     dev = torch.device("cuda:0")
     if a.profile_backward or a.profile_per_step:
         args = setup(SHAPES["trainer"]["B"], SHAPES["trainer"]["H"], dev)
@@ -136,7 +173,7 @@ def main():
             one_iteration(rollout_forward if a.profile_backward else per_step_forward, *args)
         return
     for name in (["trainer", "reference"] if a.shape == "both" else [a.shape]):
-        bench(name, a.repeats, a.window, dev)
+        bench(name, a.repeats, a.window, dev, ck)
 
 
 if __name__ == "__main__":
