@@ -5,9 +5,10 @@ The HIP kernels live in csrc/ and are built into libgnca.so (C ABI: include/gnca
 """
 from .damage import DamagePolicy, regrow_trace
 from .modules import FixedSobelPerception, GraphAugmentation, NeuralCA, NeuralCAGraph
+from .modules._stepper import TangentResult
 from .render import CMAPS, colorize, render_rgb
 from .vitals import StateVitals, state_vitals
 
 __all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph",
            "render_rgb", "colorize", "CMAPS", "DamagePolicy", "regrow_trace",
-           "state_vitals", "StateVitals"]
+           "state_vitals", "StateVitals", "TangentResult"]

@@ -130,6 +130,16 @@ class RolloutTaps(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+TANGENT_RENORM = 1 << 0   # gnca_tangent_args.flags: renormalise the tangent at every recorded step
+
+
+class TangentArgs(ctypes.Structure):
+    """Mirror of gnca_tangent_args (include/gnca.h): record is a HOST array read during the call, log_norm
+    a device pointer; the stream travels in the struct."""
+    _fields_ = [("num_records", ctypes.c_int32), ("record", ctypes.c_void_p), ("flags", ctypes.c_uint32),
+                ("log_norm", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
 OPTIM_MAX_TENSORS = 24
 OPTIM_ONE_LAUNCH_MAX = 65536   # elements a one-launch gnca_optim_step call may hold (include/gnca.h)
 OPTIM_POLICY_NONE, OPTIM_POLICY_NORMALIZE, OPTIM_POLICY_CLIP = 0, 1, 2
@@ -214,7 +224,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_trace_diag", "gnca_render_u8", "gnca_colorize_u8", "gnca_damage_policy",
            "gnca_state_vitals_workspace_bytes", "gnca_state_vitals",
            "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals",
-           "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps", "gnca_rollout_fwd_taps")
+           "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps", "gnca_rollout_fwd_taps",
+           "gnca_step_tangent_workspace_bytes", "gnca_step_tangent",
+           "gnca_rollout_tangent_workspace_bytes", "gnca_rollout_tangent")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -389,6 +401,19 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_fwd_taps.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                   ctypes.POINTER(RolloutSched), ctypes.POINTER(RolloutTaps),
                                                   vp, vp, vp, sz, vp, vp, vp, sz]
+        if hasattr(lib, "gnca_step_tangent"):   # (likewise)
+            ta = ctypes.POINTER(TangentArgs)
+            lib.gnca_step_tangent_workspace_bytes.restype = sz
+            lib.gnca_step_tangent_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc)]
+            lib.gnca_step_tangent.restype = ctypes.c_int
+            lib.gnca_step_tangent.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights), vp, vp, vp, vp, vp,
+                                              vp, vp, sz, vp]
+            lib.gnca_rollout_tangent_workspace_bytes.restype = sz
+            lib.gnca_rollout_tangent_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc),
+                                                                 ctypes.POINTER(RolloutSched), ta]
+            lib.gnca_rollout_tangent.restype = ctypes.c_int
+            lib.gnca_rollout_tangent.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                 ctypes.POINTER(RolloutSched), ta, vp, vp, vp, vp, vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

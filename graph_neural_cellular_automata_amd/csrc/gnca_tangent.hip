@@ -1,0 +1,856 @@
+// gnca_tangent.hip — forward-mode tangent (Jacobian-vector product) of the NCA step and of a whole
+// scheduled rollout: gnca_step_tangent / gnca_rollout_tangent (include/gnca.h).
+//
+// One step x -> x' carries v -> v' with the conventions of the backward (the alive, sender and fire
+// masks are constants, the perception bank is frozen, torus offset weights are the constant 1/k):
+//
+//   primal   the forward's own step (gnca_step_masked_phases, all phases): x', and in its workspace the
+//            dense update field dxb and the GroupNorm partials
+//   T0  gnca_t_prep      the pre-update alive / sender mask bytes of x, and (mu, rstd) per sample
+//   TA  gnca_t_mlp       u' = fire * A_pre * (W2 ([hpre > 0] * W1 perceive(v)) + message tangent), dense,
+//                        and per 32-cell tile the fp64 partials of sum u' and sum xhat * u'
+//   TB  gnca_t_finalize  v' = v + gain * (1 - t^2) * GroupNorm'(u'), alpha gated by the post-update mask
+//   TN  gnca_t_sumsq / gnca_t_lognorm / gnca_t_scale   at a tapped step: the log norm, renormalisation
+//
+// TA is persistent.  A wave owns 32 consecutive cells of one sample: the cells are the columns of
+// v_mfma_f32_32x32x2_f32 tiles, so each of the 64 lanes holds one cell (lane & 31) and one of the two
+// k values of a k-step (lane >> 5).  The weights sit in LDS in the order the A operand reads them;
+// x and v are read straight from global memory (9 stencil taps per channel serve the identity and
+// both Sobel features, for x and v alike), so there is no staged tile, no tile planner and no shape
+// class without a plan.  The hidden layer's accumulator is the second product's B operand as it
+// stands: a lane holds hidden rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of each 32-row block, and the
+// W2 image is read in that k order.
+#include <algorithm>
+#include <mutex>
+#include <unordered_map>
+
+#include "gnca_device.h"
+
+namespace gnca {
+namespace {
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+
+constexpr int kTile = 32;          // cells per wave tile (the MFMA's N)
+constexpr int NW_ = kThreads / 64;  // waves per workgroup
+constexpr uint32_t kTMsg = 1u << 8;   // the message term is on this step
+constexpr uint32_t kTGN = 1u << 9;    // GroupNorm
+
+__host__ __device__ inline int even2(int v) { return (v + 1) & ~1; }
+
+// Masked loads.  A `keep ? load : 0` select (or its integer-mask form) lets the compiler branch around
+// every load and wait out one memory latency per element.  The loads here are unconditional and the value
+// is multiplied by a 0 / 1 float, which the compiler may not fold into a select, so a batch's loads are all
+// in flight together.  Every masked-out load is redirected to an address whose value reaches the same
+// output cell anyway: an off-image tap and a dead sender read the receiving cell itself, a padded channel
+// reads a real channel of the same cell (C - 1 for the taps, 0 in the gather).  So a non-finite value under a
+// zero mask (NaN where a select would give 0) can only be the cell's own, which makes its result NaN in any
+// case; a NaN in a dead sender's cell does not reach the cells that would have heard from it.
+// hidden row of accumulator register r of a 32x32 MFMA tile on lane half h
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+struct TLds {   // float offsets of the weight images in TA's dynamic LDS
+  int HP, CPe, w1, b1, w2, wm, bm, wp, total;
+};
+
+__host__ __device__ inline TLds t_lds(int C, int hidden, int slice) {
+  TLds L;
+  L.CPe = even2(C);
+  L.HP = (hidden + slice - 1) / slice * slice;
+  L.w1 = 0;
+  L.b1 = L.w1 + 3 * L.CPe * L.HP;
+  L.w2 = L.b1 + L.HP;
+  L.wm = L.w2 + L.HP * 32;
+  L.bm = L.wm + L.CPe * 32;
+  L.wp = L.bm + 32;
+  L.total = L.wp + r4(27 * L.CPe);
+  return L;
+}
+
+// ------------------------------------------------------------------------------------------
+// T0: mask bytes of x (bit 0: pre-update alive, bit 1: sender alive) and the primal's (mu, rstd)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void gnca_t_prep(const float* x, const double* stats, const uint8_t* active,
+                                                       uint8_t* masks, float* coef, int C, int H, int W, int tps,
+                                                       float thr, float gthr, float eps, int use_gn) {
+  const int b = blockIdx.y;
+  if (active && !active[b]) return;
+  const size_t HW = (size_t)H * W;
+  const float* a = x + ((size_t)b * C + 3) * HW;
+  for (int cell = blockIdx.x * kThreads + threadIdx.x; cell < (int)HW; cell += gridDim.x * kThreads) {
+    const int i = cell / W, j = cell - i * W;
+    float mx = -INFINITY;
+    for (int ii = max(0, i - 1); ii <= min(H - 1, i + 1); ++ii)
+      for (int jj = max(0, j - 1); jj <= min(W - 1, j + 1); ++jj) mx = fmaxf(mx, a[(size_t)ii * W + jj]);
+    masks[(size_t)b * HW + cell] = (uint8_t)((mx > thr ? 1 : 0) | (mx > gthr ? 2 : 0));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) {
+    float mu = 0.f, rs = 1.f;
+    if (use_gn) {
+      double t1, t2;   // wave_sum2, as the forward K2: the same mean / rstd
+      wave_sum2(stats + (size_t)b * tps * 2, tps, &t1, &t2);
+      const double n = (double)C * (double)HW;
+      const double m = t1 / n;
+      double var = t2 / n - m * m;
+      if (var < 0.0) var = 0.0;
+      mu = (float)m;
+      rs = (float)(1.0 / sqrt(var + (double)eps));
+    }
+    if (threadIdx.x == 0) {
+      coef[2 * b] = mu;
+      coef[2 * b + 1] = rs;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// TA: the tangent MLP kernel
+// ------------------------------------------------------------------------------------------
+struct TAArgs {
+  const float* x;
+  const float* v;
+  const float* dx;        // the primal's dense update field (after fire and the pre mask)
+  const uint8_t* masks;
+  const float* coef;      // [B][2]: mu, rstd
+  const void* fire;
+  const uint8_t* active;
+  const float *perc, *w1, *b1, *w2, *wm, *bm;
+  float* ud;              // [B,C,H,W]: u', zeros at dead and unfired cells
+  double* part;           // [B][ntile][2]: sum u', sum xhat u' of the tile
+  int B, C, H, W, hidden, k, ntile, total, fire_mode;
+  uint32_t flags;
+  float fire_rate, message_gain, invk;
+  uint64_t seed;
+  int64_t rng_step, sample_base;
+  int8_t off[2 * GNCA_MAX_OFFSETS];
+};
+
+template <int NB>   // 32-row hidden blocks per slice
+__global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int C = a.C, H = a.H, W = a.W, Hd = a.hidden;
+  const TLds L = t_lds(C, Hd, 32 * NB);
+  const int HP = L.HP, CPe = L.CPe;
+  float* w1s = smem + L.w1;
+  float* b1s = smem + L.b1;
+  float* w2s = smem + L.w2;
+  float* wms = smem + L.wm;
+  float* bms = smem + L.bm;
+  float* wps = smem + L.wp;
+  const bool msg = (a.flags & kTMsg) != 0, gn = (a.flags & kTGN) != 0;
+  // weight images
+  lds_fill<kThreads, 8>(w1s, 3 * CPe * HP, tid, [&](int idx) {
+    const int kk = idx / HP, hid = idx - kk * HP, f = kk / CPe, c = kk - f * CPe;
+    return (c < C && hid < Hd) ? a.w1[(size_t)hid * 3 * C + f * C + c] : 0.f;
+  });
+  lds_fill<kThreads, 4>(b1s, HP, tid, [&](int idx) { return idx < Hd ? a.b1[idx] : 0.f; });
+  lds_fill<kThreads, 8>(w2s, HP * 32, tid, [&](int idx) {
+    const int hid = idx >> 5, co = idx & 31;
+    return (co < C && hid < Hd) ? a.w2[(size_t)co * Hd + hid] : 0.f;
+  });
+  lds_fill<kThreads, 4>(wms, CPe * 32, tid, [&](int idx) {
+    const int ci = idx >> 5, co = idx & 31;
+    return (msg && ci < C && co < C) ? a.wm[co * C + ci] : 0.f;
+  });
+  lds_fill<kThreads, 1>(bms, 32, tid, [&](int idx) { return (msg && idx < C) ? a.bm[idx] : 0.f; });
+  lds_fill<kThreads, 4>(wps, 27 * CPe, tid, [&](int idx) { return idx < 27 * C ? a.perc[idx] : 0.f; });
+  __syncthreads();
+
+  const int col = lane & 31, h = lane >> 5;
+  const int HW = H * W;
+  const size_t sHW = (size_t)HW;
+  for (int wt = blockIdx.x * NW_ + wave; wt < a.total; wt += gridDim.x * NW_) {
+    const int b = wt / a.ntile, tile = wt - b * a.ntile;
+    if (a.active && !a.active[b]) continue;
+    const int cell = tile * kTile + col;
+    const bool valid = cell < HW;
+    const int i = valid ? cell / W : 0, j = valid ? cell - i * W : 0;
+    const uint8_t* mb = a.masks + (size_t)b * sHW;
+    const bool pre = valid && (mb[cell] & 1);
+    const bool live = pre && fire_at(a.fire_mode, a.fire, a.fire_rate, a.seed, a.rng_step, a.sample_base, b, sHW,
+                                     (size_t)cell);
+    float* udb = a.ud + (size_t)b * C * sHW;
+    double* outp = a.part + ((size_t)b * a.ntile + tile) * 2;
+    if (__ballot(live) == 0ull) {   // nothing fires in this tile: u' = 0 (wave-uniform branch)
+      if (valid)
+        for (int c = h; c < C; c += 2) udb[(size_t)c * sHW + cell] = 0.f;
+      if (lane == 0) {
+        outp[0] = 0.0;
+        outp[1] = 0.0;
+      }
+      continue;
+    }
+    const float* xb = a.x + (size_t)b * C * sHW;
+    const float* vb = a.v + (size_t)b * C * sHW;
+    // the 9 stencil taps of this lane's cell (zero padding: perception.py:16)
+    int nidx[9];
+    bool nok[9];
+    float nmask[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int ii = i + t / 3 - 1, jj = j + t % 3 - 1;
+      nok[t] = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
+      nidx[t] = nok[t] ? ii * W + jj : (valid ? cell : 0);
+      nmask[t] = nok[t] ? 1.f : 0.f;
+    }
+    f16v accu;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accu[r] = 0.f;
+    for (int hb = 0; hb < HP; hb += 32 * NB) {
+      f16v accy[NB], accv[NB];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          accy[nb][r] = 0.f;
+          accv[nb][r] = 0.f;
+        }
+      // hpre and W1 perceive(v): both B columns share one pass over the W1 image
+      const int nsp = CPe / 2;
+      auto load_taps = [&](int sp, float (&xo)[9], float (&vo)[9]) {   // raw: masked where they are used
+        const int c = min(2 * sp + h, C - 1);
+        const float* xc = xb + (size_t)c * sHW;
+        const float* vc = vb + (size_t)c * sHW;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          xo[t] = xc[nidx[t]];
+          vo[t] = vc[nidx[t]];
+        }
+      };
+      auto products = [&](int sp, const float (&xi)[9], const float (&vi)[9]) {
+        const int c = 2 * sp + h;
+        const float cm = c < C ? 1.f : 0.f;
+        float xm[9], vm[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          xm[t] = xi[t] * (nmask[t] * cm);
+          vm[t] = vi[t] * (nmask[t] * cm);
+        }
+        const float* wp = wps + c * 27;   // (c < CPe: zeros past C)
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {
+          float y = 0.f, yd = 0.f;
+#pragma unroll
+          for (int t = 0; t < 9; ++t) {
+            const float wv = wp[f * 9 + t];
+            y = fmaf(wv, xm[t], y);
+            yd = fmaf(wv, vm[t], yd);
+          }
+          const float* wrow = w1s + (size_t)(f * CPe + c) * HP + hb + col;
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) {
+            const float wa = wrow[32 * nb];
+            accy[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, y, accy[nb], 0, 0, 0);
+            accv[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, yd, accv[nb], 0, 0, 0);
+          }
+        }
+      };
+      // two tap sets: the next channel pair's 18 loads are issued before this pair's products
+      float xa[9], va[9], xq[9], vq[9];
+      load_taps(0, xa, va);
+      for (int sp = 0; sp < nsp; sp += 2) {
+        load_taps(min(sp + 1, nsp - 1), xq, vq);
+        products(sp, xa, va);
+        if (sp + 1 < nsp) {
+          load_taps(min(sp + 2, nsp - 1), xa, va);
+          products(sp + 1, xq, vq);
+        }
+      }
+      // h' = [hpre > 0] * (W1 y'), then u' += W2 h' with the accumulator as the B operand
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int hid = hb + 32 * nb + acc_row(r, h);
+          const float hd = (accy[nb][r] + b1s[hid]) > 0.f ? accv[nb][r] : 0.f;
+          accu = __builtin_amdgcn_mfma_f32_32x32x2f32(w2s[hid * 32 + col], hd, accu, 0, 0, 0);
+        }
+    }
+    // the message and its tangent: Wm (1/k sum_o shift_o(A_send z)) for z = x and z = v
+    f16v accm, accd;
+    float cnt = 0.f;
+    if (msg) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        accm[r] = 0.f;
+        accd[r] = 0.f;
+      }
+      const bool a2a = (a.flags & GNCA_ALIVE_TO_ALIVE) != 0;
+      // four channel pairs per pass over the offsets, instead of one load latency per (channel pair, offset)
+      for (int sp0 = 0; sp0 < CPe / 2; sp0 += 4) {
+        float gx[4], gv[4];
+        const float* xc[4];
+        const float* vc[4];
+        float cokf[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = 2 * (sp0 + u) + h;
+          cokf[u] = (c < C && valid) ? 1.f : 0.f;
+          xc[u] = xb + (size_t)(c < C ? c : 0) * sHW;
+          vc[u] = vb + (size_t)(c < C ? c : 0) * sHW;
+          gx[u] = 0.f;
+          gv[u] = 0.f;
+        }
+        float ns = 0.f;
+        // eight offsets at a time: their 8 mask bytes in one memory latency, then their 64 loads in another
+        for (int o0 = 0; o0 < a.k; o0 += 8) {
+          int q[8];
+          uint8_t mq[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int o = min(o0 + e, a.k - 1);
+            q[e] = wrapi(i - (int)a.off[2 * o], H) * W + wrapi(j - (int)a.off[2 * o + 1], W);
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) mq[e] = mb[q[e]];
+          float xl[8][4], vl[8][4], sm[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const bool s = (o0 + e < a.k) & (!a2a | ((mq[e] & 2) != 0));
+            sm[e] = s ? 1.f : 0.f;
+            ns += (valid && s) ? 1.f : 0.f;
+            q[e] = s ? q[e] : (valid ? cell : 0);   // a dead sender is not read: the cell itself, under a zero mask
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              xl[e][u] = xc[u][q[e]];
+              vl[e][u] = vc[u][q[e]];
+            }
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              gx[u] = fmaf(xl[e][u], sm[e] * cokf[u], gx[u]);
+              gv[u] = fmaf(vl[e][u], sm[e] * cokf[u], gv[u]);
+            }
+        }
+        cnt = ns * a.invk;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = 2 * (sp0 + u) + h;   // (past CPe: a zero row of the padded Wm image is never read)
+          const float wa = c < CPe ? wms[c * 32 + col] : 0.f;
+          accm = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, gx[u] * a.invk, accm, 0, 0, 0);
+          accd = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, gv[u] * a.invk, accd, 0, 0, 0);
+        }
+      }
+    }
+    // epilogue: the message tangent, the fire and pre masks, the dense store and the tile's partials
+    float mu = 0.f, rs = 1.f;
+    if (gn) {
+      mu = a.coef[2 * b];
+      rs = a.coef[2 * b + 1];
+    }
+    const float* dxb = a.dx + (size_t)b * C * sHW;
+    const bool honly = (a.flags & GNCA_HIDDEN_ONLY) != 0;
+    double su = 0.0, sux = 0.0;
+    float dxv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {   // the 16 loads of the primal field together (clamped addresses)
+      const int c = min(acc_row(r, h), C - 1);
+      dxv[r] = gn ? dxb[(size_t)c * sHW + (valid ? cell : 0)] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = acc_row(r, h);
+      const bool ok = c < C && valid;
+      float u = accu[r];
+      if (msg) {
+        const float tm = tanhf(accm[r] + bms[min(c, 31)] * cnt);
+        u += (honly && c < 4) ? 0.f : a.message_gain * (1.f - tm * tm) * accd[r];
+      }
+      u = (live && ok) ? u : 0.f;
+      if (ok) udb[(size_t)c * sHW + cell] = u;
+      const float xh = (dxv[r] - mu) * rs;
+      su += (double)u;
+      sux += (double)u * (double)xh;   // (u is 0 where the lane holds no cell or channel)
+    }
+    if (gn) {
+      for (int off = 32; off > 0; off >>= 1) {
+        su += __shfl_xor(su, off);
+        sux += __shfl_xor(sux, off);
+      }
+      if (lane == 0) {
+        outp[0] = su;
+        outp[1] = sux;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// TB: GroupNorm tangent, tanh', residual and the alpha post gate (from x')
+// ------------------------------------------------------------------------------------------
+struct TBArgs {
+  const float *x, *x_out, *v, *dx, *ud, *coef, *gamma, *beta;
+  const double* part;
+  const uint8_t* active;
+  float* v_out;
+  int B, C, H, W, ntile;
+  float gain, thr;
+  int use_gn;
+};
+
+__global__ __launch_bounds__(kThreads) void gnca_t_finalize(const TBArgs a) {
+  __shared__ float sh[2];
+  const int b = blockIdx.y, C = a.C, H = a.H, W = a.W;
+  const int HW = H * W;
+  const size_t sHW = (size_t)HW;
+  const int cell = blockIdx.x * kThreads + threadIdx.x;
+  const size_t base = (size_t)b * C * sHW;
+  if (a.active && !a.active[b]) {   // the step left this sample alone: v passes through
+    if (cell < HW)
+      for (int c = 0; c < C; ++c) a.v_out[base + (size_t)c * sHW + cell] = a.v[base + (size_t)c * sHW + cell];
+    return;
+  }
+  const bool gn = a.use_gn != 0;
+  if (gn) {
+    if (threadIdx.x < 64) {
+      double su, sux;   // the tiles' partials in wave_sum2's fixed order
+      wave_sum2(a.part + (size_t)b * a.ntile * 2, a.ntile, &su, &sux);
+      const double n = (double)C * (double)HW;
+      if (threadIdx.x == 0) {
+        sh[0] = (float)(su / n);
+        sh[1] = (float)(sux / n);
+      }
+    }
+    __syncthreads();
+  }
+  if (cell >= HW) return;
+  const float mu = gn ? a.coef[2 * b] : 0.f, rs = gn ? a.coef[2 * b + 1] : 1.f;
+  const float mu_u = gn ? sh[0] : 0.f, mu_ux = gn ? sh[1] : 0.f;
+  // post-update alive mask.  thr >= 0: from the gated alpha of x', exactly: a cell is alive iff a
+  // neighbour's updated alpha exceeds thr, and that neighbour is then alive itself, so its alpha passed
+  // the gate; a gated alpha is +-0 and never exceeds thr.  thr < 0: a gated +-0 would exceed it, so the
+  // neighbours' updated alpha before the gate is recomputed with the forward K2's expression (as the
+  // backward's BA does: the same gate bits)
+  const int i = cell / W, j = cell - i * W;
+  float mx = -INFINITY;
+  if (a.thr >= 0.f) {
+    const float* ao = a.x_out + base + 3 * sHW;
+    for (int ii = max(0, i - 1); ii <= min(H - 1, i + 1); ++ii)
+      for (int jj = max(0, j - 1); jj <= min(W - 1, j + 1); ++jj) mx = fmaxf(mx, ao[(size_t)ii * W + jj]);
+  } else {
+    const float* ax = a.x + base + 3 * sHW;
+    const float* ad = a.dx + base + 3 * sHW;
+    const float g3 = gn ? a.gamma[3] : 1.f, b3 = gn ? a.beta[3] : 0.f;
+    for (int ii = max(0, i - 1); ii <= min(H - 1, i + 1); ++ii)
+      for (int jj = max(0, j - 1); jj <= min(W - 1, j + 1); ++jj) {
+        const size_t q = (size_t)ii * W + jj;
+        float d = ad[q];
+        if (gn) d = (d - mu) * rs * g3 + b3;
+        mx = fmaxf(mx, ax[q] + fast_tanh(d) * a.gain);
+      }
+  }
+  const float post = mx > a.thr ? 1.f : 0.f;
+  for (int c = 0; c < C; ++c) {
+    const size_t p = base + (size_t)c * sHW + cell;
+    const float d = a.dx[p], u = a.ud[p], vv = a.v[p];
+    float xn = d, un = u;
+    if (gn) {
+      const float gc = a.gamma[c], xh = (d - mu) * rs;
+      xn = xh * gc + a.beta[c];
+      un = gc * rs * (u - mu_u - xh * mu_ux);
+    }
+    const float t = tanhf(xn);
+    float o = vv + a.gain * (1.f - t * t) * un;
+    if (c == 3) o *= post;
+    a.v_out[p] = o;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// TN: the log norm of a tapped step, and the renormalisation
+// ------------------------------------------------------------------------------------------
+constexpr int kNormChunk = 16 * kThreads;   // elements of one sample per workgroup
+
+__global__ __launch_bounds__(kThreads) void gnca_t_sumsq(const float* v, double* pn, size_t n, int nchunk) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const float* vb = v + (size_t)b * n;
+  double s = 0.0;
+  for (int u = 0; u < 16; ++u) {
+    const size_t e = (size_t)chunk * kNormChunk + (size_t)u * kThreads + threadIdx.x;
+    const double f = e < n ? (double)vb[e] : 0.0;
+    s += f * f;
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) pn[(size_t)b * nchunk + chunk] = ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// one wave per sample: S = sum v'^2, log_norm = 0.5 log S + the carried log of earlier renormalisations
+__global__ __launch_bounds__(64) void gnca_t_lognorm(const double* pn, int nchunk, double* carry, float* scale,
+                                                     double* log_norm, int renorm) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double s = 0.0;
+  for (int t = lane; t < nchunk; t += 64) s += pn[(size_t)b * nchunk + t];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  s = __shfl(s, 0);
+  if (lane != 0) return;
+  const double half_log = 0.5 * log(s);   // -inf for a zero tangent
+  log_norm[b] = half_log + carry[b];
+  float sc = 1.f;
+  if (renorm && s > 0.0 && s < INFINITY) {
+    sc = (float)(1.0 / sqrt(s));
+    carry[b] += half_log;
+  }
+  scale[b] = sc;
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_t_scale(float* v, const float* scale, size_t n) {
+  const int b = blockIdx.y;
+  const float sc = scale[b];
+  if (sc == 1.f) return;
+  float* vb = v + (size_t)b * n;
+  for (int u = 0; u < 16; ++u) {
+    const size_t e = (size_t)blockIdx.x * kNormChunk + (size_t)u * kThreads + threadIdx.x;
+    if (e < n) vb[e] *= sc;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void gnca_t_zero_f64(double* p, int n) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i < n) p[i] = 0.0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host
+// ------------------------------------------------------------------------------------------
+int t_check() {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    g_last_hip = (int)e;
+    return GNCA_ERR_HIP;
+  }
+  return GNCA_OK;
+}
+
+int t_device_cus() {
+  static std::mutex mu;
+  static std::unordered_map<int, int> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int cus = 256;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  cache[dev] = cus;
+  return cus;
+}
+
+// The step's workspace: [forward step workspace | u' | mask bytes | coef | tile partials]
+struct TanLayout {
+  FwdLayout F;
+  size_t off_fwd, off_ud, off_masks, off_coef, off_part, bytes;
+  int ntile, NB;
+  bool msg, gn;
+};
+
+bool tangent_unsupported(const gnca_step_desc* d) {
+  return (d->flags & GNCA_GRAPH) && (d->flags & GNCA_ZERO_PAD_SHIFT) && d->num_offsets > 0;
+}
+
+// a well-formed shape outside the compiled support set (gnca_status_string names it)
+bool outside_support(const gnca_step_desc* d) {
+  if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C < 4 || d->hidden <= 0) return false;
+  return d->C > 32 || d->hidden > ((d->C >= 13 && d->C <= 16) ? 256 : 128);
+}
+
+bool tan_layout(const gnca_step_desc* desc, TanLayout* T) {
+  if (!desc) return false;
+  gnca_step_desc d = *desc;
+  d.flags &= ~GNCA_ATTENTION;
+  if (tangent_unsupported(&d)) return false;
+  if (!fwd_layout(&d, &T->F)) return false;
+  const size_t HW = (size_t)d.H * d.W, n = (size_t)d.B * d.C * HW;
+  T->ntile = (int)((HW + kTile - 1) / kTile);
+  if ((size_t)d.B * T->ntile > 0x7fffffffull) return false;
+  T->NB = d.hidden <= 32 ? 1 : d.hidden <= 64 ? 2 : 4;
+  T->msg = (d.flags & GNCA_GRAPH) && d.num_offsets > 0 && d.message_gain != 0.f;
+  T->gn = (d.flags & GNCA_USE_GROUPNORM) != 0;
+  size_t o = 0;
+  T->off_fwd = o;   o += align256(T->F.ws_bytes);
+  T->off_ud = o;    o += align256(n * sizeof(float));
+  T->off_masks = o; o += align256((size_t)d.B * HW);
+  T->off_coef = o;  o += align256((size_t)d.B * 2 * sizeof(float));
+  T->off_part = o;  o += align256((size_t)d.B * T->ntile * 2 * sizeof(double));
+  T->bytes = o;
+  return true;
+}
+
+// the largest step workspace of a schedule (the forward plan varies with the message and the offsets' reach)
+bool tan_sched_bytes(const gnca_step_desc* d, const gnca_rollout_sched* s, size_t* out) {
+  TanLayout T;
+  if (!tan_layout(d, &T)) return false;
+  size_t m = T.bytes;
+  uint32_t seen[64];
+  int ns = 0;
+  for (int t = 0; t < s->steps; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(d, s, t, &sd);
+    int ry = 0, rx = 0;
+    for (int o = 0; o < sd.num_offsets; ++o) {
+      ry = std::max(ry, std::abs((int)sd.offsets[2 * o]));
+      rx = std::max(rx, std::abs((int)sd.offsets[2 * o + 1]));
+    }
+    const uint32_t key = (sd.message_gain != 0.f ? 1u << 16 : 0u) | ((uint32_t)ry << 8) | (uint32_t)rx;
+    bool hit = false;
+    for (int q = 0; q < ns; ++q) hit = hit || seen[q] == key;
+    if (hit) continue;
+    if (ns < 64) seen[ns++] = key;
+    if (!tan_layout(&sd, &T)) return false;
+    m = std::max(m, T.bytes);
+  }
+  *out = m;
+  return true;
+}
+
+template <int NB>
+int launch_ta(const TAArgs& a, int C, int hidden, hipStream_t st) {
+  const TLds L = t_lds(C, hidden, 32 * NB);
+  const size_t lds = (size_t)L.total * sizeof(float);
+  auto fn = gnca_t_mlp<NB>;
+  // the dynamic-LDS attribute and the resident workgroups per CU (registers and LDS decide), set and asked
+  // once per (device, LDS size)
+  static std::mutex mu;
+  static std::unordered_map<uint64_t, int> cache;
+  int per_cu = 0, dev = 0;
+  (void)hipGetDevice(&dev);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t key = ((uint64_t)(uint32_t)dev << 32) | (uint64_t)lds;
+    auto it = cache.find(key);
+    if (it != cache.end()) per_cu = it->second;
+    else {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), kThreads, lds) !=
+              hipSuccess || per_cu < 1)
+        per_cu = 1;
+      cache[key] = per_cu = std::min(per_cu, 2);
+    }
+  }
+  const long want = ((long)a.total + NW_ - 1) / NW_;
+  const int grid = (int)std::max<long>(1, std::min<long>(want, (long)t_device_cus() * per_cu));
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), lds, st, a);
+  return t_check();
+}
+
+// One step and its tangent.  carry / taps are the rollout's business: this is the body of both entry points.
+int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
+                      hipStream_t st) {
+  gnca_step_desc d = *desc;
+  d.flags &= ~GNCA_ATTENTION;
+  TanLayout T;
+  if (!tan_layout(&d, &T)) return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < T.bytes) return GNCA_ERR_WORKSPACE;
+  char* wsb = reinterpret_cast<char*>(ws);
+  int rc = gnca_step_masked_phases(&d, w, x, x_out, fire, active, wsb + T.off_fwd, T.F.ws_bytes, st, GNCA_PHASE_ALL);
+  if (rc != GNCA_OK) return rc;
+  const int B = d.B, C = d.C, H = d.H, W = d.W;
+  const int HW = H * W;
+  const float* dx = reinterpret_cast<const float*>(wsb + T.off_fwd + T.F.off_dx);
+  const double* stats = reinterpret_cast<const double*>(wsb + T.off_fwd + T.F.off_stats);
+  float* ud = reinterpret_cast<float*>(wsb + T.off_ud);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb + T.off_masks);
+  float* coef = reinterpret_cast<float*>(wsb + T.off_coef);
+  double* part = reinterpret_cast<double*>(wsb + T.off_part);
+  const int ncb = (HW + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(gnca_t_prep, dim3((unsigned)std::min(ncb, 64), (unsigned)B), dim3(kThreads), 0, st, x, stats,
+                     active, masks, coef, C, H, W, T.F.tps, d.alpha_thr, d.graph_alpha_thr, d.gn_eps, T.gn ? 1 : 0);
+  if ((rc = t_check()) != GNCA_OK) return rc;
+  {
+    TAArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.v = v; a.dx = dx; a.masks = masks; a.coef = coef; a.fire = fire; a.active = active;
+    a.perc = w->perception; a.w1 = w->w1; a.b1 = w->b1; a.w2 = w->w2; a.wm = w->wm; a.bm = w->bm;
+    a.ud = ud; a.part = part;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.hidden = d.hidden; a.k = T.msg ? d.num_offsets : 0;
+    a.ntile = T.ntile; a.total = B * T.ntile; a.fire_mode = d.fire_mode;
+    a.flags = (d.flags & (GNCA_ALIVE_TO_ALIVE | GNCA_HIDDEN_ONLY)) | (T.msg ? kTMsg : 0u) | (T.gn ? kTGN : 0u);
+    a.fire_rate = d.fire_rate; a.message_gain = d.message_gain;
+    a.invk = a.k > 0 ? (float)(1.0 / (double)a.k) : 0.f;
+    a.seed = d.rng_seed; a.rng_step = d.rng_step; a.sample_base = d.sample_base;
+    for (int o = 0; o < 2 * a.k; ++o) a.off[o] = d.offsets[o];
+    rc = T.NB == 1 ? launch_ta<1>(a, C, d.hidden, st)
+                   : T.NB == 2 ? launch_ta<2>(a, C, d.hidden, st) : launch_ta<4>(a, C, d.hidden, st);
+    if (rc != GNCA_OK) return rc;
+  }
+  {
+    TBArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.x_out = x_out; a.v = v; a.dx = dx; a.ud = ud; a.coef = coef; a.gamma = w->gn_weight; a.beta = w->gn_bias;
+    a.part = part; a.active = active; a.v_out = v_out;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.ntile = T.ntile;
+    a.gain = d.update_gain; a.thr = d.alpha_thr; a.use_gn = T.gn ? 1 : 0;
+    hipLaunchKernelGGL(gnca_t_finalize, dim3((unsigned)ncb, (unsigned)B), dim3(kThreads), 0, st, a);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+  }
+  return GNCA_OK;
+}
+
+bool distinct(const void* const* p, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      if (p[i] == p[j]) return false;
+  return true;
+}
+
+bool records_ok(const gnca_rollout_sched* s, const gnca_tangent_args* a) {
+  if (!a || a->num_records < 0) return false;
+  if (a->flags & ~(uint32_t)GNCA_TANGENT_RENORM) return false;
+  if (a->num_records == 0) return true;
+  if (!a->record) return false;
+  int prev = 0;
+  for (int r = 0; r < a->num_records; ++r) {
+    if (a->record[r] <= prev || a->record[r] > s->steps) return false;
+    prev = a->record[r];
+  }
+  return true;
+}
+
+// [masks [T][B] | step workspace | 2 x states | 2 x tangents | norm partials | carry | scale]
+struct RollTanLayout {
+  size_t masks, step_ws, state, off_pn, off_carry, off_scale, bytes;
+  int nchunk;
+};
+
+bool roll_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_tangent_args* a,
+                     RollTanLayout* R) {
+  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !records_ok(s, a)) return false;
+  size_t sw;
+  if (!tan_sched_bytes(d, s, &sw)) return false;
+  const size_t n = (size_t)d->C * d->H * d->W;
+  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
+  R->step_ws = align256(sw);
+  R->state = align256((size_t)d->B * n * sizeof(float));
+  R->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
+  size_t o = R->masks + R->step_ws + 4 * R->state;
+  R->off_pn = o;    o += align256((size_t)d->B * R->nchunk * sizeof(double));
+  R->off_carry = o; o += align256((size_t)d->B * sizeof(double));
+  R->off_scale = o; o += align256((size_t)d->B * sizeof(float));
+  R->bytes = o;
+  return true;
+}
+
+}  // namespace
+}  // namespace gnca
+
+using namespace gnca;
+
+extern "C" {
+
+size_t gnca_step_tangent_workspace_bytes(const gnca_step_desc* desc) {
+  TanLayout T;
+  return tan_layout(desc, &T) ? T.bytes : 0;
+}
+
+int gnca_step_tangent(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
+                      void* hip_stream) {
+  if (!desc || !w || !x || !v || !x_out || !v_out) return GNCA_ERR_INVALID;
+  const void* ptrs[] = {x, x_out, v_out};
+  const void* ptrs2[] = {v, x_out, v_out};
+  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
+  TanLayout T;
+  if (!tan_layout(desc, &T)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  StreamDeviceGuard dg(st);
+  return step_tangent_impl(desc, w, x, fire, active, v, x_out, v_out, ws, ws_bytes, st);
+}
+
+size_t gnca_rollout_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                            const gnca_tangent_args* args) {
+  RollTanLayout R;
+  if (!desc || !sched || !args || tangent_unsupported(desc)) return 0;
+  return roll_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
+}
+
+int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const gnca_tangent_args* args, const float* x, const float* v, float* x_final,
+                         float* v_final, void* ws, size_t ws_bytes) {
+  if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
+  const void* ptrs[] = {x, x_final, v_final};
+  const void* ptrs2[] = {v, x_final, v_final};
+  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
+  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
+  if (!sched_ok(desc, sched) || !records_ok(sched, args)) return GNCA_ERR_INVALID;
+  if (args->num_records > 0 && !args->log_norm) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
+  RollTanLayout R;
+  if (!roll_tan_layout(desc, sched, args, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && sched->steps > 0 &&
+      !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(args->stream);
+  StreamDeviceGuard dg(st);
+  const int T = sched->steps, B = desc->B;
+  const size_t n = (size_t)desc->C * desc->H * desc->W, nbytes = (size_t)B * n * sizeof(float);
+  char* wsb = reinterpret_cast<char*>(ws);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + R.masks;
+  float* xp[2], *vp[2];
+  for (int q = 0; q < 2; ++q) {
+    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
+    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)(2 + q) * R.state);
+  }
+  double* pn = reinterpret_cast<double*>(wsb + R.off_pn);
+  double* carry = reinterpret_cast<double*>(wsb + R.off_carry);
+  float* scale = reinterpret_cast<float*>(wsb + R.off_scale);
+  int rc;
+  if (T == 0) {
+    hipError_t e = hipMemcpyAsync(x_final, x, nbytes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(v_final, v, nbytes, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) {
+      g_last_hip = (int)e;
+      return GNCA_ERR_HIP;
+    }
+    return GNCA_OK;
+  }
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  if (args->num_records > 0) {
+    hipLaunchKernelGGL(gnca_t_zero_f64, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, carry,
+                       B);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+  }
+  const float* xc = x;
+  const float* vc = v;
+  int r = 0;
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* xn = t == T - 1 ? x_final : xp[t & 1];
+    float* vn = t == T - 1 ? v_final : vp[t & 1];
+    rc = step_tangent_impl(&sd, w, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), vc,
+                           xn, vn, step_ws, R.step_ws, st);
+    if (rc != GNCA_OK) return rc;
+    xc = xn;
+    vc = vn;
+    if (r < args->num_records && args->record[r] == t + 1) {
+      const dim3 g((unsigned)R.nchunk, (unsigned)B);
+      const int renorm = (args->flags & GNCA_TANGENT_RENORM) ? 1 : 0;
+      hipLaunchKernelGGL(gnca_t_sumsq, g, dim3(kThreads), 0, st, (const float*)vn, pn, n, R.nchunk);
+      if ((rc = t_check()) != GNCA_OK) return rc;
+      hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, R.nchunk, carry,
+                         scale, args->log_norm + (size_t)r * B, renorm);
+      if ((rc = t_check()) != GNCA_OK) return rc;
+      if (renorm) {
+        hipLaunchKernelGGL(gnca_t_scale, g, dim3(kThreads), 0, st, vn, (const float*)scale, n);
+        if ((rc = t_check()) != GNCA_OK) return rc;
+      }
+      ++r;
+    }
+  }
+  return GNCA_OK;
+}
+
+}  // extern "C"

@@ -624,3 +624,144 @@ def run_trace(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_only:
                 attn_u8 = R.colorize(attn, render["cmap"])
     return TraceResult(out, frm, list(plan.record), attn, met, diag, rgb_u8=rgb_u8, attention_u8=attn_u8,
                        vitals=vit)
+
+
+# ---------------------------------------------------------------------------------------------
+# Forward-mode tangent: where a nudge of the state is after the step / the rollout, no tape
+# ---------------------------------------------------------------------------------------------
+class TangentResult:
+    """What ``rollout_tangent()`` returns: ``x_final`` [B,C,H,W], exactly the no-grad ``rollout()``'s
+    result; ``v_final`` [B,C,H,W], the tangent after the last step (renormalised at every recorded step
+    with ``renormalize=True``); ``steps``, the R recorded step indices (from 1); ``log_norm`` float64
+    [R,B], the natural log of the 2-norm the tangent of each sample would have after each recorded step
+    had it never been renormalised (``-inf`` for a zero tangent).  All detached."""
+
+    __slots__ = ("x_final", "v_final", "steps", "log_norm")
+
+    def __init__(self, x_final, v_final, steps, log_norm):
+        self.x_final, self.v_final, self.steps, self.log_norm = x_final, v_final, steps, log_norm
+
+    def __repr__(self):
+        return f"TangentResult(steps={self.steps}, log_norm={tuple(self.log_norm.shape)})"
+
+
+def _check_tangent_pair(model: nn.Module, x, v):
+    """ValueError unless x and v are two [B,C,H,W] tensors of one shape, device and dtype (pure Python)."""
+    for name, t in (("state", x), ("tangent", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be [B,C,H,W], got {tuple(getattr(t, 'shape', ()))}")
+    if x.shape[1] != model.n_channels:
+        raise ValueError(f"state has {x.shape[1]} channels, model expects {model.n_channels}")
+    if x.shape[1] < 4:
+        raise ValueError("the alive mask reads channel 3: n_channels must be >= 4")
+    if v.shape != x.shape:
+        raise ValueError(f"the tangent has shape {tuple(v.shape)}, the state {tuple(x.shape)}")
+    if v.device != x.device:
+        raise ValueError(f"the tangent is on {v.device}, the state on {x.device}")
+    if v.dtype != x.dtype:
+        raise ValueError(f"the tangent is {v.dtype}, the state {x.dtype}")
+
+
+def _tangent_flags(model: nn.Module, graph, hidden_only: bool):
+    """(flags, eps, k) of the model's steps, refusing what the tangent does not cover (ValueError)."""
+    flags, eps = _check_norm(model)
+    k = 0
+    if graph is not None:
+        flags |= graph.flags(False)
+        if hidden_only:
+            flags |= L.HIDDEN_ONLY
+        k = min(graph.num_neighbors, len(graph.offsets))
+    S.check_tangent_desc(flags, k)
+    return flags, eps, k
+
+
+def run_tangent_step(model: nn.Module, x, v, fire_rate, graph, message_gain, hidden_only: bool, *, active=None,
+                     offsets=None, fire=None):
+    """The shared body of ``NeuralCA.tangent_step`` / ``NeuralCAGraph.tangent_step``."""
+    _check_tangent_pair(model, x, v)
+    B, C, H, W = x.shape
+    flags, eps, _ = _tangent_flags(model, graph, hidden_only)
+    if isinstance(fire_rate, bool) or not isinstance(fire_rate, (int, float)):
+        raise ValueError(f"fire_rate must be a number, got {fire_rate!r}")
+    if offsets is not None:
+        if graph is None:
+            raise ValueError("offsets given for a model without the graph term")
+        try:
+            offsets = [tuple(o) for o in offsets]
+        except TypeError:
+            raise ValueError(f"offsets must be a sequence of (dy, dx) pairs, got {offsets!r}") from None
+        for pair in offsets:
+            if len(pair) != 2 or not all(isinstance(q, int) and -127 <= q <= 127 for q in pair):
+                raise ValueError(f"offset {pair!r} is not a (dy, dx) pair in the int8 range")
+        if len(offsets) > L.MAX_OFFSETS:
+            raise ValueError(f"at most {L.MAX_OFFSETS} offsets per step (got {len(offsets)})")
+    fire_mode = L.FIRE_NONE
+    if fire is not None:
+        if not isinstance(fire, torch.Tensor) or tuple(fire.shape) != (B, 1, H, W):
+            raise ValueError(f"fire must be a tensor of shape ({B}, 1, {H}, {W})")
+        if fire.device != x.device:
+            raise ValueError(f"fire is on {fire.device}, the state on {x.device}")
+        if fire.dtype == torch.float32:
+            fire_mode = L.FIRE_RAND_F32
+        elif fire.dtype in (torch.uint8, torch.bool):
+            fire_mode = L.FIRE_MASK_U8
+        else:
+            raise ValueError(f"fire must be float32 uniforms or a uint8 / bool mask, got {fire.dtype}")
+    if active is not None and (not isinstance(active, torch.Tensor) or active.device != x.device or
+                               active.dtype not in (torch.bool, torch.uint8) or tuple(active.shape) != (B,)):
+        raise ValueError("active must be a [B] bool/uint8 tensor on the state's device")
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)
+        v = S._dev_f32(v.detach(), "tangent")
+        # the draws of forward(): one random.sample, then (rate below 1) one torch.rand on x.device
+        chosen = None
+        if graph is not None:
+            chosen = graph.sample_offsets() if offsets is None else offsets
+        if fire is None and fire_rate < 1.0:
+            fire = torch.rand(B, 1, H, W, device=x.device)
+            fire_mode = L.FIRE_RAND_F32
+        elif fire is not None:
+            fire = fire.contiguous()
+            fire = fire.view(torch.uint8) if fire.dtype == torch.bool else fire
+        tensors = _step_tensors(model, graph)
+        alpha_thr = float(model.alpha_thr)
+        key = (B, C, H, W, tensors["w1"].shape[0], 1 if graph is None else graph.d_model, flags,
+               float(model.update_gain), alpha_thr, alpha_thr if graph is None else float(graph.alpha_thr),
+               float(eps))
+        desc = _step_desc(key, chosen, message_gain, fire_rate, fire_mode)
+        w, keep = S.make_weights(tensors)
+        out = S.step_tangent(desc, w, x, v, fire=fire, active=active)
+        del keep
+    return out
+
+
+def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool, *, every=None, record=None,
+                        renormalize=False, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0, fire=None,
+                        seed=None, sample_base=0, offsets=None) -> TangentResult:
+    """The shared body of ``NeuralCA.rollout_tangent`` / ``NeuralCAGraph.rollout_tangent``."""
+    _check_tangent_pair(model, x, v)
+    B, C, H, W = x.shape
+    _tangent_flags(model, graph, hidden_only)
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    if not isinstance(renormalize, bool):
+        raise ValueError(f"renormalize must be a bool, got {renormalize!r}")
+    # the taps follow trace()'s rules; neither every nor record: nothing is recorded
+    rec = [] if every is None and record is None else S.expand_record(steps, 1 if every is None else every, record)
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
+        v = S._dev_f32(v.detach(), "tangent")
+        if graph is not None and offsets is None:
+            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
+            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                             seed=0 if seed is None else seed, sample_base=sample_base,
+                             offsets=[[] for _ in range(steps)])
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                 sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+        x_final, v_final, log_norm = S.rollout_tangent(S.RolloutCall(desc, sched), w, x, v, rec, renormalize)
+        del keep
+    return TangentResult(x_final, v_final, list(rec), log_norm)

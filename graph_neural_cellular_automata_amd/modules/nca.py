@@ -3,8 +3,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
-                       run_step, run_trace)
+from ._stepper import (RolloutObjective, TangentResult, TraceResult, run_rollout, run_rollout_memory,
+                       run_rollout_objective, run_rollout_tangent, run_step, run_tangent_step, run_trace)
 from .perception import FixedSobelPerception
 
 
@@ -36,6 +36,20 @@ class NeuralCA(nn.Module):
         """One CA step on the HIP path (nca.py:64-105).  ``active``: see NeuralCAGraph.forward."""
         out, _ = run_step(self, x, fire_rate, None, None, 0.0, False, False, active=active)
         return out
+
+    def tangent_step(self, x: torch.Tensor, v: torch.Tensor, fire_rate: float = 1.0, *, active=None, fire=None):
+        """One CA step and its forward-mode tangent, ``(x_out, J(x) v)``: see
+        ``NeuralCAGraph.tangent_step`` (no ``offsets`` here)."""
+        return run_tangent_step(self, x, v, fire_rate, None, 0.0, False, active=active, fire=fire)
+
+    def rollout_tangent(self, x: torch.Tensor, v: torch.Tensor, steps: int, *, every=None, record=None,
+                        renormalize: bool = False, fire_rate=1.0, nsteps=None, min_steps: int = 0, fire=None,
+                        seed=None, sample_base: int = 0) -> TangentResult:
+        """The tangent of a whole rollout with no tape and its per-sample log-norm curve: see
+        ``NeuralCAGraph.rollout_tangent`` (no ``message_gain`` / ``offsets`` here)."""
+        return run_rollout_tangent(self, x, v, steps, None, False, every=every, record=record,
+                                   renormalize=renormalize, fire_rate=fire_rate, nsteps=nsteps,
+                                   min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
                 fire=None, seed=None, sample_base: int = 0, recompute: bool = False,

@@ -12,8 +12,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
-                       run_step, run_trace)
+from ._stepper import (RolloutObjective, TangentResult, TraceResult, run_rollout, run_rollout_memory,
+                       run_rollout_objective, run_rollout_tangent, run_step, run_tangent_step, run_trace)
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -70,6 +70,48 @@ class NeuralCAGraph(nn.Module):
         out, attn = run_step(self, x, fire_rate, self.graph, chosen, self.message_gain,
                              self.hidden_only, return_attention, active=active)
         return (out, attn) if return_attention else out
+
+    def tangent_step(self, x: torch.Tensor, v: torch.Tensor, fire_rate: float = 1.0, *, active=None, offsets=None,
+                     fire=None):
+        """One CA step and its forward-mode tangent (extension, not in the reference): ``(x_out, v_out)``
+        with ``x_out`` bitwise ``forward``'s result and ``v_out = J(x) v``, the Jacobian-vector product of
+        the step at ``x``, by one native call (``gnca_step_tangent``) that keeps no tape.
+
+        The conventions are the backward's: the pre- and post-update alive masks, the sender mask and
+        the fire mask are constants, the perception bank is frozen, the torus offset weights are 1/k.
+        ``offsets=None`` draws ``self.graph.sample_offsets()`` and ``fire=None`` with a rate below 1
+        draws ``torch.rand(B,1,H,W)`` on ``x.device``: Python's ``random`` and torch's generator are
+        consumed exactly as ``forward`` consumes them.  ``offsets``: a list of (dy, dx) pairs; ``fire``:
+        a [B,1,H,W] tensor of float32 uniforms or a uint8 / bool mask; ``active``: as ``forward``'s (an
+        inactive sample passes ``x`` and ``v`` through).  Always runs under ``no_grad`` and returns
+        detached tensors.  Torus mode only: a model built with ``graph_zero_padded_shift=True`` raises
+        ``ValueError`` (its offset weights depend on the state)."""
+        return run_tangent_step(self, x, v, fire_rate, self.graph, self.message_gain, self.hidden_only,
+                                active=active, offsets=offsets, fire=fire)
+
+    def rollout_tangent(self, x: torch.Tensor, v: torch.Tensor, steps: int, *, every=None, record=None,
+                        renormalize: bool = False, fire_rate=1.0, message_gain=None, nsteps=None,
+                        min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
+                        offsets=None) -> TangentResult:
+        """The tangent of a whole rollout (extension, not in the reference): where the nudge ``v`` of the
+        state ``x`` is after ``steps`` steps, carried forward beside the state in one native call
+        (``gnca_rollout_tangent``) with no tape, O(1) memory in ``steps``.
+
+        Returns a ``TangentResult``: ``x_final``, bitwise the no-grad ``rollout()``'s result on the same
+        schedule; ``v_final``, bitwise the chain of ``tangent_step`` calls; ``steps``, the recorded step
+        indices; ``log_norm`` float64 [R,B], the log of the tangent's 2-norm per sample after each
+        recorded step.  The schedule keywords mean what they mean in ``rollout()``; the taps follow
+        ``trace()``'s rules (``every=n`` or ``record=[...]``; neither: nothing is recorded).
+        ``renormalize=True`` rescales each sample's tangent to norm 1 on the device after every recorded
+        step and carries the logs, so ``log_norm`` stays the un-renormalised curve while ``v`` cannot
+        overflow: ``log_norm[-1] / steps`` is a finite-time Lyapunov exponent, with no host wait.
+        Always runs under ``no_grad`` and returns detached tensors.  Bad arguments raise ``ValueError``
+        before anything is drawn or launched.  Torus mode only (see ``tangent_step``)."""
+        return run_rollout_tangent(self, x, v, steps, self.graph, self.hidden_only, every=every, record=record,
+                                   renormalize=renormalize, fire_rate=fire_rate,
+                                   message_gain=self.message_gain if message_gain is None else message_gain,
+                                   nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                   sample_base=sample_base, offsets=offsets)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
                 min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,

@@ -963,3 +963,68 @@ class RolloutTaps:
         c.target = target.data_ptr()
         c.target_bstride = 0 if target.shape[0] == 1 else target.stride(0)
         self.c, self.record, self._keep = c, list(record), (arr, target)
+
+
+# ---------------------------------------------------------------------------------------------
+# Forward-mode tangent (gnca_step_tangent / gnca_rollout_tangent)
+# ---------------------------------------------------------------------------------------------
+ZERO_PAD_TANGENT = ("the tangent of the zero-padded shift is not implemented: its offset weights depend on the "
+                    "state through the pooled logits, so its tangent needs a second reduction pass over v; "
+                    "build the model with graph_zero_padded_shift=False (torus mode)")
+
+
+def _tangent_entry(name: str):
+    fn = getattr(L.load(), name, None)
+    if fn is None:
+        raise L.GncaError(f"libgnca.so has no {name}: rebuild it (python -c 'import __graft_entry__ as g; "
+                          f"g.build(force=True)')")
+    return fn
+
+
+def check_tangent_desc(flags: int, num_offsets: int) -> None:
+    """ValueError for what the tangent entry points refuse, before anything is drawn or launched."""
+    if (flags & L.GRAPH) and (flags & L.ZERO_PAD_SHIFT) and num_offsets > 0:
+        raise ValueError(ZERO_PAD_TANGENT)
+
+
+def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None):
+    """One step and its Jacobian-vector product: (x_out, v_out), x_out bitwise ``step``'s."""
+    fn = _tangent_entry("gnca_step_tangent")
+    lib = L.load()
+    x_out, v_out = torch.empty_like(x), torch.empty_like(v)
+    if ws is None:
+        n = lib.gnca_step_tangent_workspace_bytes(ctypes.byref(desc))
+        if n == 0:
+            raise L.GncaError(f"unsupported tangent step: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                              f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
+        ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    act = _active_u8(active, desc.B, x.device)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), _ptr(fire), _ptr(act), v.data_ptr(),
+            x_out.data_ptr(), v_out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
+    L.check(rc, "gnca_step_tangent")
+    return x_out, v_out
+
+
+def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormalize: bool):
+    """(x_final, v_final, log_norm float64 [R,B]) of the schedule bound in ``call``."""
+    fn = _tangent_entry("gnca_rollout_tangent")
+    lib = L.load()
+    desc, dev = call.desc, x.device
+    a = L.TangentArgs()
+    a.num_records = len(record)
+    arr = (ctypes.c_int32 * max(1, len(record)))(*record)
+    a.record = ctypes.cast(arr, ctypes.c_void_p) if record else None
+    a.flags = L.TANGENT_RENORM if renormalize else 0
+    log_norm = torch.empty(len(record), desc.B, dtype=torch.float64, device=dev)
+    a.log_norm = log_norm.data_ptr() if record else None
+    a.stream = stream_ptr(dev)
+    n = lib.gnca_rollout_tangent_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(a))
+    if n == 0:
+        raise L.GncaError(f"unsupported tangent rollout: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    x_final, v_final = torch.empty_like(x), torch.empty_like(v)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
+            v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
+    L.check(rc, "gnca_rollout_tangent")
+    return x_final, v_final, log_norm

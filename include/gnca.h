@@ -1024,6 +1024,78 @@ typedef struct gnca_colorize_desc { int32_t N, H, W, norm; void* stream; } gnca_
 int gnca_colorize_u8(const gnca_colorize_desc* d, const float* maps, const uint8_t* lut, uint8_t* out);
       /* maps [N,H,W] contiguous; out [N,H,W,3] contiguous, 4-byte aligned */
 
+/* ---------------------------------------------------------------------------------------------
+ * Forward-mode tangent (Jacobian-vector product) of the step and of a scheduled rollout (DESIGN.md
+ * section 21): where a nudge v of the state is after T steps, carried forward beside the state with
+ * no tape, O(1) memory in T.  Neither name carries the _f32 suffix, and the stream is named
+ * hip_stream or travels in the args struct.
+ *
+ * The conventions are the backward's (gnca_step_bwd_f32): the pre- and post-update alive masks, the
+ * sender mask and the fire mask are constants, the perception bank is frozen, and in torus mode the
+ * offset weights are the constant 1/k.  With hpre, m (the message before tanh, after the hidden-only
+ * zeroing), xhat, rstd and t = tanh(xn) the primal step's own intermediates at x, one step x -> x'
+ * carries v -> v':
+ *   y'  = perceive(v)
+ *   h'  = [hpre > 0] (W1 y')                                                        (no bias)
+ *   u'  = W2 h' + message_gain (1 - tanh^2(m)) hidden_only(sum_o w_o shift_o(A_send (Wm v)))
+ *   u'  = u' fire A_pre
+ *   xn' = gamma rstd (u' - mean(u') - xhat mean(xhat u'))    (per-sample means over C*H*W; without
+ *                                                             GroupNorm xn' = u')
+ *   v'  = v + update_gain (1 - t^2) xn';   v'[:, 3] *= post_alive(x')
+ * A sample that a masked or nsteps step leaves alone passes v through unchanged, as it does x.
+ *
+ * The one gap: the zero-padded shift (GNCA_ZERO_PAD_SHIFT on a graph step with offsets), whose offset
+ * weights depend on x, is GNCA_ERR_UNSUPPORTED (workspace size 0).
+ * Fixed-order fp64 sums, no float atomics: bitwise reproducible, and a sample's results do not
+ * depend on the other samples.  One stream, no allocation, no host synchronisation, capturable.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_TANGENT_RENORM (1u << 0)  /* renormalise v' of each sample at every recorded step */
+
+typedef struct gnca_tangent_args {
+  int32_t num_records;     /* R >= 0                                                           */
+  const int32_t* record;   /* HOST [R], strictly increasing, in 1..sched->steps                */
+  uint32_t flags;          /* GNCA_TANGENT_RENORM                                              */
+  double* log_norm;        /* DEVICE [R][B] or NULL when R = 0                                 */
+  void* stream;            /* hipStream_t, NULL = the null stream                              */
+} gnca_tangent_args;
+
+/* Bytes of device workspace gnca_step_tangent needs for `desc` (0 on an invalid or unsupported desc).
+ * Host-only. */
+size_t gnca_step_tangent_workspace_bytes(const gnca_step_desc* desc);
+
+/*
+ * One step and its tangent: x_out = step(x), bitwise gnca_step_f32's (gnca_step_masked_f32's with
+ * `active`), and v_out = J(x) v.  fire / active as in those two entry points (active may be NULL).
+ * x and v are read; x_out and v_out are written completely and must alias neither each other nor x
+ * or v (GNCA_ERR_INVALID, as for a null pointer, before any launch).  ws: 256-B aligned.
+ */
+int gnca_step_tangent(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws,
+                      size_t ws_bytes, void* hip_stream);
+
+/* Bytes of device workspace gnca_rollout_tangent needs (0 on an invalid or unsupported desc, schedule
+ * or record list).  Host-only: reads the schedule's and the args' host arrays.  Apart from the [T][B]
+ * step masks it does not grow with T. */
+size_t gnca_rollout_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                            const gnca_tangent_args* args);
+
+/*
+ * The tangent of a whole rollout on the schedule gnca_rollout_fwd_f32 reads (offsets, per-step
+ * fire_rate / message_gain, nsteps, full_steps, fire); GNCA_SCHED_RECOMPUTE and GNCA_SCHED_CHECKPOINT
+ * are GNCA_ERR_INVALID (there is no tape).  x_final is bitwise gnca_rollout_fwd_f32's without a tape,
+ * v_final the chain of gnca_step_tangent calls.  GNCA_ERR_INVALID before any launch for a null
+ * pointer, aliasing between x / v and the outputs, or a malformed record list.
+ *   log_norm[r][b]  the natural log of the 2-norm the tangent of sample b would have after step
+ *                   record[r] had it never been renormalised: 0.5 log(sum v'^2) (fp64, fixed order)
+ *                   plus the sample's carried log of earlier renormalisations; -inf for a zero tangent
+ *   GNCA_TANGENT_RENORM  after the norm is recorded, v' of that sample is multiplied by
+ *                   (float)(1 / sqrt(sum v'^2)) when the sum is positive and finite, and left alone
+ *                   otherwise.  The host never waits.
+ */
+int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const gnca_tangent_args* args, const float* x, const float* v, float* x_final,
+                         float* v_final, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
