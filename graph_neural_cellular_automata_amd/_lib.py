@@ -140,6 +140,18 @@ class TangentArgs(ctypes.Structure):
                 ("log_norm", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
 
 
+TANGENT_MAX_DIRS = 16          # GNCA_TANGENT_MAX_DIRS: directions of a tangent block
+TANGENT_QR_CHUNK = 4096        # GNCA_TANGENT_QR_CHUNK: elements of one sample per Gram partial
+TBLOCK_ORTHO = 1 << 0          # gnca_tangent_block_args.flags: replace the block by Q at every recorded step
+
+
+class TangentBlockArgs(ctypes.Structure):
+    """Mirror of gnca_tangent_block_args (include/gnca.h): record is a HOST array read during the call, log_r a
+    device pointer; the stream travels in the struct."""
+    _fields_ = [("num_dirs", ctypes.c_int32), ("num_records", ctypes.c_int32), ("record", ctypes.c_void_p),
+                ("flags", ctypes.c_uint32), ("log_r", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
 OPTIM_MAX_TENSORS = 24
 OPTIM_ONE_LAUNCH_MAX = 65536   # elements a one-launch gnca_optim_step call may hold (include/gnca.h)
 OPTIM_POLICY_NONE, OPTIM_POLICY_NORMALIZE, OPTIM_POLICY_CLIP = 0, 1, 2
@@ -226,7 +238,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_trace_vitals_workspace_bytes", "gnca_rollout_trace_vitals",
            "gnca_rollout_tap_loss", "gnca_rollout_bwd_taps", "gnca_rollout_fwd_taps",
            "gnca_step_tangent_workspace_bytes", "gnca_step_tangent",
-           "gnca_rollout_tangent_workspace_bytes", "gnca_rollout_tangent")
+           "gnca_rollout_tangent_workspace_bytes", "gnca_rollout_tangent",
+           "gnca_tangent_qr_workspace_bytes", "gnca_tangent_qr",
+           "gnca_rollout_tangent_block_workspace_bytes", "gnca_rollout_tangent_block")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -414,6 +428,18 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_tangent.restype = ctypes.c_int
             lib.gnca_rollout_tangent.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                  ctypes.POINTER(RolloutSched), ta, vp, vp, vp, vp, vp, sz]
+        if hasattr(lib, "gnca_tangent_qr"):   # (likewise)
+            tb = ctypes.POINTER(TangentBlockArgs)
+            lib.gnca_tangent_qr_workspace_bytes.restype = sz
+            lib.gnca_tangent_qr_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+            lib.gnca_tangent_qr.restype = ctypes.c_int
+            lib.gnca_tangent_qr.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, sz, vp]
+            lib.gnca_rollout_tangent_block_workspace_bytes.restype = sz
+            lib.gnca_rollout_tangent_block_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc),
+                                                                       ctypes.POINTER(RolloutSched), tb]
+            lib.gnca_rollout_tangent_block.restype = ctypes.c_int
+            lib.gnca_rollout_tangent_block.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
+                                                       ctypes.POINTER(RolloutSched), tb, vp, vp, vp, vp, vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -11,6 +11,9 @@
 //                        and per 32-cell tile the fp64 partials of sum u' and sum xhat * u'
 //   TB  gnca_t_finalize  v' = v + gain * (1 - t^2) * GroupNorm'(u'), alpha gated by the post-update mask
 //   TN  gnca_t_sumsq / gnca_t_lognorm / gnca_t_scale   at a tapped step: the log norm, renormalisation
+//   TQ  gnca_t_gram / gnca_t_factor / gnca_t_apply     the thin QR of a block of K tangents (gnca_tangent_qr), which
+//                        gnca_rollout_tangent_block runs at a tapped step; that rollout runs
+//                        the primal step and T0 once per step and TA, TB once per direction
 //
 // TA is persistent.  A wave owns 32 consecutive cells of one sample: the cells are the columns of
 // v_mfma_f32_32x32x2_f32 tiles, so each of the 64 lanes holds one cell (lane & 31) and one of the two
@@ -483,8 +486,9 @@ __global__ __launch_bounds__(kThreads) void gnca_t_sumsq(const float* v, double*
 }
 
 // one wave per sample: S = sum v'^2, log_norm = 0.5 log S + the carried log of earlier renormalisations
+// (log_norm[b * stride]: the block rollout records direction j of [B][K] with stride K)
 __global__ __launch_bounds__(64) void gnca_t_lognorm(const double* pn, int nchunk, double* carry, float* scale,
-                                                     double* log_norm, int renorm) {
+                                                     double* log_norm, int renorm, int stride) {
   const int b = blockIdx.x, lane = threadIdx.x;
   double s = 0.0;
   for (int t = lane; t < nchunk; t += 64) s += pn[(size_t)b * nchunk + t];
@@ -492,7 +496,7 @@ __global__ __launch_bounds__(64) void gnca_t_lognorm(const double* pn, int nchun
   s = __shfl(s, 0);
   if (lane != 0) return;
   const double half_log = 0.5 * log(s);   // -inf for a zero tangent
-  log_norm[b] = half_log + carry[b];
+  log_norm[(size_t)b * stride] = half_log + carry[b];
   float sc = 1.f;
   if (renorm && s > 0.0 && s < INFINITY) {
     sc = (float)(1.0 / sqrt(s));
@@ -515,6 +519,162 @@ __global__ __launch_bounds__(kThreads) void gnca_t_scale(float* v, const float* 
 __global__ __launch_bounds__(kThreads) void gnca_t_zero_f64(double* p, int n) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i < n) p[i] = 0.0;
+}
+
+// ------------------------------------------------------------------------------------------
+// TQ: the thin QR of a tangent block v [K][B][n] (gnca_tangent_qr)
+//   TQ1 gnca_t_gram    per (sample, chunk) the fp64 Gram partials of all K (K + 1) / 2 pairs
+//   TQ2 gnca_t_factor  one wave per sample: G, its Cholesky factor with the pivot rule, Rinv, the logs
+//   TQ3 gnca_t_apply   Q = V Rinv, in place
+// ------------------------------------------------------------------------------------------
+typedef double d4v __attribute__((ext_vector_type(4)));
+
+constexpr int kMaxDirs = GNCA_TANGENT_MAX_DIRS;
+constexpr int kQrChunk = GNCA_TANGENT_QR_CHUNK;   // elements of one sample per Gram workgroup
+constexpr int kQrWave = kQrChunk / NW_;           // ... per wave: kQrWave / 4 k-steps of v_mfma_f64_16x16x4_f64
+constexpr int kApplyPer = 2;                      // elements per thread of TQ3
+constexpr int kApplyChunk = kApplyPer * kThreads;
+static_assert(kMaxDirs == 16 && kQrWave % 32 == 0, "the Gram tile is the 16x16 MFMA's");
+
+// The directions are the 16 rows AND the 16 columns of the MFMA (zero rows past K), the elements its k
+// dimension: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], which for V^T V is one and
+// the same value, direction l & 15 at element 4 s + (l >> 4) of k-step s.  A lane's load is 4 bytes and a
+// wave's covers 16 B of each direction; the 8 k-steps in flight together cover 128 B of each.
+__global__ __launch_bounds__(kThreads) void gnca_t_gram(const float* v, double* part, size_t n, size_t dstride,
+                                                        int K, int nchunk) {
+  __shared__ double red[NW_][256];
+  const int b = blockIdx.x / nchunk, chunk = blockIdx.x - b * nchunk;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = lane & 15, kq = lane >> 4;
+  const bool dok = d < K;
+  const float* vd = v + (size_t)min(d, K - 1) * dstride + (size_t)b * n;
+  const size_t e0 = (size_t)chunk * kQrChunk + (size_t)wave * kQrWave;
+  d4v acc = {0.0, 0.0, 0.0, 0.0};
+  for (int s0 = 0; s0 < kQrWave / 4; s0 += 8) {
+    if (e0 + 4 * (size_t)s0 >= n) break;   // (wave-uniform)
+    float f[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const size_t e = e0 + 4 * (size_t)(s0 + u) + kq;
+      f[u] = vd[e < n ? e : n - 1];        // (clamped: never past the sample; the value is dropped below)
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const size_t e = e0 + 4 * (size_t)(s0 + u) + kq;
+      const double a = (dok && e < n) ? (double)f[u] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
+    }
+  }
+  // C/D of the f64 MFMA: register g of lane l is row (l >> 4) + 4 g, column l & 15
+#pragma unroll
+  for (int g = 0; g < 4; ++g) red[wave][g * 64 + lane] = acc[g];
+  __syncthreads();
+  const int g = tid >> 6, row = (lane >> 4) + 4 * g, col = lane & 15;
+  if (row <= col && col < K) {
+    const int npair = K * (K + 1) / 2;
+    part[((size_t)b * nchunk + chunk) * npair + col * (col + 1) / 2 + row] =
+        (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  }
+}
+
+// One wave per sample.  rinv [B][16][16] (row-major, zero outside the kept rows and columns): every entry is
+// written.  r / log_out / carry may be null; log_out[b][j] = log R_jj (+ carry[b][j], which then takes the log).
+__global__ __launch_bounds__(64) void gnca_t_factor(const double* part, int nchunk, int K, double* rinv, double* r,
+                                                    double* log_out, double* carry) {
+  __shared__ double G[kMaxDirs][kMaxDirs + 1], R[kMaxDirs][kMaxDirs + 1], X[kMaxDirs][kMaxDirs + 1];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int npair = K * (K + 1) / 2;
+  for (int idx = lane; idx < kMaxDirs * kMaxDirs; idx += 64) {
+    const int i = idx >> 4, j = idx & 15;
+    R[i][j] = 0.0;
+    X[i][j] = 0.0;
+    if (i <= j && j < K) {
+      const double* p = part + (size_t)b * nchunk * npair + j * (j + 1) / 2 + i;
+      double s = 0.0;
+      for (int c = 0; c < nchunk; ++c) s += p[(size_t)c * npair];   // the chunks in order
+      G[i][j] = s;
+      G[j][i] = s;
+    }
+  }
+  __syncthreads();
+  const int k = lane;
+  double logd = 0.0;   // lane j: log R_jj
+  bool kept = false;   // lane j: column j was not dropped
+  for (int j = 0; j < K; ++j) {
+    const bool mine = k >= j && k < K;
+    double s = 0.0;
+    if (mine)
+      for (int i = 0; i < j; ++i) s += R[i][j] * R[i][k];
+    const double val = mine ? G[j][k] - s : 0.0;
+    const double dj = __shfl(val, j);
+    const bool ok = dj > 0.0 && dj < INFINITY && dj > 0x1p-44 * G[j][j];
+    const double rjj = ok ? sqrt(dj) : 0.0;
+    if (k == j) {
+      kept = ok;
+      logd = ok ? log(rjj) : -INFINITY;
+    }
+    if (k < kMaxDirs) R[j][k] = (ok && mine) ? (k == j ? rjj : val / rjj) : 0.0;
+    __syncthreads();
+  }
+  // Rinv, column m on lane m: back substitution over the kept rows; dropped rows and columns stay zero
+  if (k < K && kept) {
+    const int m = k;
+    X[m][m] = 1.0 / R[m][m];
+    for (int i = m - 1; i >= 0; --i) {
+      if (R[i][i] == 0.0) continue;
+      double s = 0.0;
+      for (int l = i + 1; l <= m; ++l) s += (R[l][l] == 0.0) ? 0.0 : R[i][l] * X[l][m];
+      X[i][m] = -s / R[i][i];
+    }
+  }
+  __syncthreads();
+  for (int idx = lane; idx < kMaxDirs * kMaxDirs; idx += 64) {
+    const int i = idx >> 4, j = idx & 15;
+    rinv[(size_t)b * kMaxDirs * kMaxDirs + idx] = X[i][j];
+    if (r && i < K && j < K) r[((size_t)b * K + i) * K + j] = R[i][j];
+  }
+  if (k < K && log_out) {
+    const size_t o = (size_t)b * K + k;
+    if (carry) {
+      log_out[o] = logd + carry[o];
+      if (kept) carry[o] += logd;
+    } else {
+      log_out[o] = logd;
+    }
+  }
+}
+
+// KB: K rounded up to 4, 8 or 16 (the unrolled triangle).  A thread reads its element's K values, one per
+// direction (a wave's loads of one direction are 256 contiguous bytes), and stores K.
+template <int KB>
+__global__ __launch_bounds__(kThreads) void gnca_t_apply(float* v, const double* rinv, size_t n, size_t dstride,
+                                                         int K, int nchunk) {
+  __shared__ double X[kMaxDirs * kMaxDirs];
+  const int b = blockIdx.x / nchunk, chunk = blockIdx.x - b * nchunk;
+  X[threadIdx.x] = rinv[(size_t)b * kMaxDirs * kMaxDirs + threadIdx.x];
+  __syncthreads();
+  float* vb = v + (size_t)b * n;
+  float f[kApplyPer][KB];
+#pragma unroll
+  for (int u = 0; u < kApplyPer; ++u) {
+    const size_t e = (size_t)chunk * kApplyChunk + (size_t)u * kThreads + threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < KB; ++i) f[u][i] = vb[(size_t)min(i, K - 1) * dstride + (e < n ? e : n - 1)];
+  }
+#pragma unroll
+  for (int u = 0; u < kApplyPer; ++u) {
+    const size_t e = (size_t)chunk * kApplyChunk + (size_t)u * kThreads + threadIdx.x;
+    double a[KB];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) a[i] = (i < K && X[i * kMaxDirs + i] != 0.0) ? (double)f[u][i] : 0.0;   // a dropped row is skipped
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+      double q = 0.0;
+#pragma unroll
+      for (int i = 0; i <= j; ++i) q = fma(a[i], X[i * kMaxDirs + j], q);
+      if (j < K && e < n) vb[(size_t)j * dstride + e] = (float)q;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -641,10 +801,10 @@ int launch_ta(const TAArgs& a, int C, int hidden, hipStream_t st) {
   return t_check();
 }
 
-// One step and its tangent.  carry / taps are the rollout's business: this is the body of both entry points.
-int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
-                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
-                      hipStream_t st) {
+// One step and its tangent, in two parts that share the step workspace: the primal part (the forward's step and
+// T0) once per step, the direction part (TA, TB) once per tangent carried through that step.
+int step_tangent_primal(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                        const uint8_t* active, float* x_out, void* ws, size_t ws_bytes, hipStream_t st) {
   gnca_step_desc d = *desc;
   d.flags &= ~GNCA_ATTENTION;
   TanLayout T;
@@ -655,16 +815,33 @@ int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const f
   if (rc != GNCA_OK) return rc;
   const int B = d.B, C = d.C, H = d.H, W = d.W;
   const int HW = H * W;
-  const float* dx = reinterpret_cast<const float*>(wsb + T.off_fwd + T.F.off_dx);
   const double* stats = reinterpret_cast<const double*>(wsb + T.off_fwd + T.F.off_stats);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb + T.off_masks);
+  float* coef = reinterpret_cast<float*>(wsb + T.off_coef);
+  const int ncb = (HW + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(gnca_t_prep, dim3((unsigned)std::min(ncb, 64), (unsigned)B), dim3(kThreads), 0, st, x, stats,
+                     active, masks, coef, C, H, W, T.F.tps, d.alpha_thr, d.graph_alpha_thr, d.gn_eps, T.gn ? 1 : 0);
+  return t_check();
+}
+
+// v -> v_out through the step whose primal part has just run in `ws` (x, x_out, fire, active as passed there)
+int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                     const uint8_t* active, const float* v, const float* x_out, float* v_out, void* ws,
+                     hipStream_t st) {
+  gnca_step_desc d = *desc;
+  d.flags &= ~GNCA_ATTENTION;
+  TanLayout T;
+  if (!tan_layout(&d, &T)) return GNCA_ERR_INVALID;
+  char* wsb = reinterpret_cast<char*>(ws);
+  int rc;
+  const int B = d.B, C = d.C, H = d.H, W = d.W;
+  const int HW = H * W;
+  const float* dx = reinterpret_cast<const float*>(wsb + T.off_fwd + T.F.off_dx);
   float* ud = reinterpret_cast<float*>(wsb + T.off_ud);
   uint8_t* masks = reinterpret_cast<uint8_t*>(wsb + T.off_masks);
   float* coef = reinterpret_cast<float*>(wsb + T.off_coef);
   double* part = reinterpret_cast<double*>(wsb + T.off_part);
   const int ncb = (HW + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(gnca_t_prep, dim3((unsigned)std::min(ncb, 64), (unsigned)B), dim3(kThreads), 0, st, x, stats,
-                     active, masks, coef, C, H, W, T.F.tps, d.alpha_thr, d.graph_alpha_thr, d.gn_eps, T.gn ? 1 : 0);
-  if ((rc = t_check()) != GNCA_OK) return rc;
   {
     TAArgs a;
     memset(&a, 0, sizeof(a));
@@ -693,6 +870,15 @@ int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const f
     if ((rc = t_check()) != GNCA_OK) return rc;
   }
   return GNCA_OK;
+}
+
+// the body of gnca_step_tangent and of gnca_rollout_tangent's steps
+int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
+                      hipStream_t st) {
+  const int rc = step_tangent_primal(desc, w, x, fire, active, x_out, ws, ws_bytes, st);
+  if (rc != GNCA_OK) return rc;
+  return step_tangent_dir(desc, w, x, fire, active, v, x_out, v_out, ws, st);
 }
 
 bool distinct(const void* const* p, int n) {
@@ -735,6 +921,86 @@ bool roll_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const
   R->off_pn = o;    o += align256((size_t)d->B * R->nchunk * sizeof(double));
   R->off_carry = o; o += align256((size_t)d->B * sizeof(double));
   R->off_scale = o; o += align256((size_t)d->B * sizeof(float));
+  R->bytes = o;
+  return true;
+}
+
+// gnca_tangent_qr's workspace: [Gram partials [B][nchunk][K (K + 1) / 2] | Rinv [B][16][16]]
+struct QrLayout {
+  size_t off_rinv, bytes;
+  int nchunk, napply;
+};
+
+bool qr_layout(int K, int B, int64_t n, QrLayout* Q) {
+  if (K < 1 || K > kMaxDirs || B < 1 || n < 1) return false;
+  const int64_t nchunk = (n + kQrChunk - 1) / kQrChunk, napply = (n + kApplyChunk - 1) / kApplyChunk;
+  if (napply * (int64_t)B > 0x7fffffffll) return false;   // (the grids are one-dimensional)
+  Q->nchunk = (int)nchunk;
+  Q->napply = (int)napply;
+  // (room for 16 directions' pairs whatever K: the block rollout's workspace is then linear in K)
+  Q->off_rinv = align256((size_t)B * (size_t)nchunk * (size_t)(kMaxDirs * (kMaxDirs + 1) / 2) * sizeof(double));
+  Q->bytes = Q->off_rinv + align256((size_t)B * kMaxDirs * kMaxDirs * sizeof(double));
+  return true;
+}
+
+// TQ1, TQ2, TQ3 on v [K] directions `dstride` elements apart; r / log_out / carry as gnca_t_factor takes them
+int launch_qr(const QrLayout& Q, int K, int B, size_t n, size_t dstride, float* v, double* r, double* log_out,
+              double* carry, char* qws, hipStream_t st) {
+  double* part = reinterpret_cast<double*>(qws);
+  double* rinv = reinterpret_cast<double*>(qws + Q.off_rinv);
+  int rc;
+  hipLaunchKernelGGL(gnca_t_gram, dim3((unsigned)((size_t)B * Q.nchunk)), dim3(kThreads), 0, st, (const float*)v, part,
+                     n, dstride, K, Q.nchunk);
+  if ((rc = t_check()) != GNCA_OK) return rc;
+  hipLaunchKernelGGL(gnca_t_factor, dim3((unsigned)B), dim3(64), 0, st, (const double*)part, Q.nchunk, K, rinv, r,
+                     log_out, carry);
+  if ((rc = t_check()) != GNCA_OK) return rc;
+  const dim3 g((unsigned)((size_t)B * Q.napply));
+  if (K <= 4)
+    hipLaunchKernelGGL(gnca_t_apply<4>, g, dim3(kThreads), 0, st, v, (const double*)rinv, n, dstride, K, Q.napply);
+  else if (K <= 8)
+    hipLaunchKernelGGL(gnca_t_apply<8>, g, dim3(kThreads), 0, st, v, (const double*)rinv, n, dstride, K, Q.napply);
+  else
+    hipLaunchKernelGGL(gnca_t_apply<16>, g, dim3(kThreads), 0, st, v, (const double*)rinv, n, dstride, K, Q.napply);
+  return t_check();
+}
+
+bool block_records_ok(const gnca_rollout_sched* s, const gnca_tangent_block_args* a) {
+  if (!a || a->num_dirs < 1 || a->num_dirs > kMaxDirs) return false;
+  if (a->flags & ~(uint32_t)GNCA_TBLOCK_ORTHO) return false;
+  gnca_tangent_args one;
+  memset(&one, 0, sizeof(one));
+  one.num_records = a->num_records;
+  one.record = a->record;
+  return records_ok(s, &one);
+}
+
+// [masks [T][B] | step workspace | 2 x states | 2 x K tangents | norm partials | scale | carry [B][K] | QR workspace]
+struct BlockTanLayout {
+  size_t masks, step_ws, state, block, off_pn, off_scale, off_carry, off_qr, bytes;
+  int nchunk;
+  QrLayout Q;
+};
+
+bool block_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_tangent_block_args* a,
+                      BlockTanLayout* R) {
+  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !block_records_ok(s, a))
+    return false;
+  size_t sw;
+  if (!tan_sched_bytes(d, s, &sw)) return false;
+  const int K = a->num_dirs;
+  const size_t n = (size_t)d->C * d->H * d->W;
+  if (!qr_layout(K, d->B, (int64_t)n, &R->Q)) return false;
+  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
+  R->step_ws = align256(sw);
+  R->state = align256((size_t)d->B * n * sizeof(float));
+  R->block = align256((size_t)K * d->B * n * sizeof(float));
+  R->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
+  size_t o = R->masks + R->step_ws + 2 * R->state + 2 * R->block;
+  R->off_pn = o;    o += align256((size_t)d->B * R->nchunk * sizeof(double));
+  R->off_scale = o; o += align256((size_t)d->B * sizeof(float));
+  R->off_carry = o; o += align256((size_t)d->B * kMaxDirs * sizeof(double));
+  R->off_qr = o;    o += R->Q.bytes;
   R->bytes = o;
   return true;
 }
@@ -841,11 +1107,121 @@ int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, cons
       hipLaunchKernelGGL(gnca_t_sumsq, g, dim3(kThreads), 0, st, (const float*)vn, pn, n, R.nchunk);
       if ((rc = t_check()) != GNCA_OK) return rc;
       hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, R.nchunk, carry,
-                         scale, args->log_norm + (size_t)r * B, renorm);
+                         scale, args->log_norm + (size_t)r * B, renorm, 1);
       if ((rc = t_check()) != GNCA_OK) return rc;
       if (renorm) {
         hipLaunchKernelGGL(gnca_t_scale, g, dim3(kThreads), 0, st, vn, (const float*)scale, n);
         if ((rc = t_check()) != GNCA_OK) return rc;
+      }
+      ++r;
+    }
+  }
+  return GNCA_OK;
+}
+
+size_t gnca_tangent_qr_workspace_bytes(int32_t num_dirs, int32_t B, int64_t n) {
+  QrLayout Q;
+  return qr_layout(num_dirs, B, n, &Q) ? Q.bytes : 0;
+}
+
+int gnca_tangent_qr(int32_t num_dirs, int32_t B, int64_t n, float* v, double* r, double* log_diag, void* ws,
+                    size_t ws_bytes, void* hip_stream) {
+  QrLayout Q;
+  if (!v || !qr_layout(num_dirs, B, n, &Q)) return GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < Q.bytes) return GNCA_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  StreamDeviceGuard dg(st);
+  return launch_qr(Q, num_dirs, B, (size_t)n, (size_t)B * (size_t)n, v, r, log_diag, nullptr,
+                   reinterpret_cast<char*>(ws), st);
+}
+
+size_t gnca_rollout_tangent_block_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                                  const gnca_tangent_block_args* args) {
+  BlockTanLayout R;
+  if (!desc || !sched || !args || tangent_unsupported(desc)) return 0;
+  return block_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
+}
+
+int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                               const gnca_tangent_block_args* args, const float* x, const float* v,
+                               float* x_final, float* v_final, void* ws, size_t ws_bytes) {
+  if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
+  const void* ptrs[] = {x, x_final, v_final};
+  const void* ptrs2[] = {v, x_final, v_final};
+  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
+  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
+  if (!sched_ok(desc, sched) || !block_records_ok(sched, args)) return GNCA_ERR_INVALID;
+  if (args->num_records > 0 && !args->log_r) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
+  BlockTanLayout R;
+  if (!block_tan_layout(desc, sched, args, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && sched->steps > 0 &&
+      !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(args->stream);
+  StreamDeviceGuard dg(st);
+  const int T = sched->steps, B = desc->B, K = args->num_dirs;
+  const size_t n = (size_t)desc->C * desc->H * desc->W, dstride = (size_t)B * n, nbytes = dstride * sizeof(float);
+  char* wsb = reinterpret_cast<char*>(ws);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + R.masks;
+  float* xp[2], *vp[2];
+  for (int q = 0; q < 2; ++q) {
+    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
+    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + 2 * R.state + (size_t)q * R.block);
+  }
+  double* pn = reinterpret_cast<double*>(wsb + R.off_pn);
+  float* scale = reinterpret_cast<float*>(wsb + R.off_scale);
+  double* carry = reinterpret_cast<double*>(wsb + R.off_carry);
+  int rc;
+  if (T == 0) {
+    hipError_t e = hipMemcpyAsync(x_final, x, nbytes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(v_final, v, (size_t)K * nbytes, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) {
+      g_last_hip = (int)e;
+      return GNCA_ERR_HIP;
+    }
+    return GNCA_OK;
+  }
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  if (args->num_records > 0) {   // (without ORTHO the first B entries serve every direction and stay zero)
+    hipLaunchKernelGGL(gnca_t_zero_f64, dim3((unsigned)((B * K + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       carry, B * K);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+  }
+  const bool ortho = (args->flags & GNCA_TBLOCK_ORTHO) != 0;
+  const float* xc = x;
+  const float* vc = v;
+  int r = 0;
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* xn = t == T - 1 ? x_final : xp[t & 1];
+    float* vn = t == T - 1 ? v_final : vp[t & 1];
+    const void* fire = sched_step_fire(desc, sched, t);
+    const uint8_t* active = sched_step_active(desc, sched, t, masks);
+    if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
+    for (int j = 0; j < K; ++j)
+      if ((rc = step_tangent_dir(&sd, w, xc, fire, active, vc + (size_t)j * dstride, xn, vn + (size_t)j * dstride,
+                                 step_ws, st)) != GNCA_OK)
+        return rc;
+    xc = xn;
+    vc = vn;
+    if (r < args->num_records && args->record[r] == t + 1) {
+      double* out = args->log_r + (size_t)r * B * K;
+      if (ortho) {
+        if ((rc = launch_qr(R.Q, K, B, n, dstride, vn, nullptr, out, carry, wsb + R.off_qr, st)) != GNCA_OK) return rc;
+      } else {
+        for (int j = 0; j < K; ++j) {
+          hipLaunchKernelGGL(gnca_t_sumsq, dim3((unsigned)R.nchunk, (unsigned)B), dim3(kThreads), 0, st,
+                             (const float*)(vn + (size_t)j * dstride), pn, n, R.nchunk);
+          if ((rc = t_check()) != GNCA_OK) return rc;
+          hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, R.nchunk, carry,
+                             scale, out + j, 0, K);
+          if ((rc = t_check()) != GNCA_OK) return rc;
+        }
       }
       ++r;
     }

@@ -765,3 +765,62 @@ def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool,
         x_final, v_final, log_norm = S.rollout_tangent(S.RolloutCall(desc, sched), w, x, v, rec, renormalize)
         del keep
     return TangentResult(x_final, v_final, list(rec), log_norm)
+
+
+class TangentBlockResult:
+    """What ``rollout_tangent_block()`` returns: ``x_final`` [B,C,H,W], exactly the no-grad ``rollout()``'s
+    result; ``v_final`` [K,B,C,H,W], the block after the last step; ``steps``, the R recorded step indices
+    (from 1); ``log_r`` float64 [R,B,K].  With ``orthonormalize=True`` ``log_r[r,b,j]`` is the running sum of
+    ``log R_jj`` over the QR factorisations up to recorded step r (``-inf`` from the record at which
+    direction j was dropped); without, it is direction j's own log norm.  All detached."""
+
+    __slots__ = ("x_final", "v_final", "steps", "log_r")
+
+    def __init__(self, x_final, v_final, steps, log_r):
+        self.x_final, self.v_final, self.steps, self.log_r = x_final, v_final, steps, log_r
+
+    def exponents(self):
+        """``log_r[-1] / steps[-1]``, float64 [B,K]: the finite-time Lyapunov spectrum over the whole
+        rollout, per step, largest first for a generic block.  A sample that ``nsteps`` stopped early ran
+        fewer steps than ``steps[-1]``: dividing its row by its own step count is the caller's."""
+        if not self.steps:
+            raise ValueError("nothing was recorded: pass every= or record=")
+        return self.log_r[-1] / self.steps[-1]
+
+    def __repr__(self):
+        return f"TangentBlockResult(steps={self.steps}, log_r={tuple(self.log_r.shape)})"
+
+
+def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only: bool, *, every=None, record=None,
+                              orthonormalize=True, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0,
+                              fire=None, seed=None, sample_base=0, offsets=None) -> TangentBlockResult:
+    """The shared body of ``NeuralCA.rollout_tangent_block`` / ``NeuralCAGraph.rollout_tangent_block``."""
+    if not isinstance(V, torch.Tensor) or V.dim() != 5:
+        raise ValueError(f"the tangent block must be [K,B,C,H,W], got {tuple(getattr(V, 'shape', ()))}")
+    if not 1 <= V.shape[0] <= L.TANGENT_MAX_DIRS:
+        raise ValueError(f"the block holds {V.shape[0]} directions; 1 <= K <= {L.TANGENT_MAX_DIRS}")
+    _check_tangent_pair(model, x, V[0])
+    B, C, H, W = x.shape
+    _tangent_flags(model, graph, hidden_only)
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    if not isinstance(orthonormalize, bool):
+        raise ValueError(f"orthonormalize must be a bool, got {orthonormalize!r}")
+    rec = [] if every is None and record is None else S.expand_record(steps, 1 if every is None else every, record)
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
+        V = S._dev_f32(V.detach(), "tangent block")
+        if graph is not None and offsets is None:
+            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
+            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                             seed=0 if seed is None else seed, sample_base=sample_base,
+                             offsets=[[] for _ in range(steps)])
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                 sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+        x_final, v_final, log_r = S.rollout_tangent_block(S.RolloutCall(desc, sched), w, x, V, rec, orthonormalize)
+        del keep
+    return TangentBlockResult(x_final, v_final, list(rec), log_r)

@@ -3,8 +3,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TangentResult, TraceResult, run_rollout, run_rollout_memory,
-                       run_rollout_objective, run_rollout_tangent, run_step, run_tangent_step, run_trace)
+from ._stepper import (RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
+                       run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
+                       run_step, run_tangent_step, run_trace)
 from .perception import FixedSobelPerception
 
 
@@ -50,6 +51,16 @@ class NeuralCA(nn.Module):
         return run_rollout_tangent(self, x, v, steps, None, False, every=every, record=record,
                                    renormalize=renormalize, fire_rate=fire_rate, nsteps=nsteps,
                                    min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
+
+    def rollout_tangent_block(self, x: torch.Tensor, V: torch.Tensor, steps: int, *, every=None, record=None,
+                              orthonormalize: bool = True, fire_rate=1.0, nsteps=None, min_steps: int = 0,
+                              fire=None, seed=None, sample_base: int = 0) -> TangentBlockResult:
+        """A block of K tangents ``V`` [K,B,C,H,W] through a whole rollout, re-orthonormalised on the
+        device at every recorded step: see ``NeuralCAGraph.rollout_tangent_block`` (no ``message_gain`` /
+        ``offsets`` here)."""
+        return run_rollout_tangent_block(self, x, V, steps, None, False, every=every, record=record,
+                                         orthonormalize=orthonormalize, fire_rate=fire_rate, nsteps=nsteps,
+                                         min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
                 fire=None, seed=None, sample_base: int = 0, recompute: bool = False,

@@ -12,8 +12,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TangentResult, TraceResult, run_rollout, run_rollout_memory,
-                       run_rollout_objective, run_rollout_tangent, run_step, run_tangent_step, run_trace)
+from ._stepper import (RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
+                       run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
+                       run_step, run_tangent_step, run_trace)
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -112,6 +113,30 @@ class NeuralCAGraph(nn.Module):
                                    message_gain=self.message_gain if message_gain is None else message_gain,
                                    nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                                    sample_base=sample_base, offsets=offsets)
+
+    def rollout_tangent_block(self, x: torch.Tensor, V: torch.Tensor, steps: int, *, every=None, record=None,
+                              orthonormalize: bool = True, fire_rate=1.0, message_gain=None, nsteps=None,
+                              min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
+                              offsets=None) -> TangentBlockResult:
+        """``rollout_tangent`` for a block of K directions ``V`` [K,B,C,H,W], 1 <= K <= 16, beside ONE
+        primal state, in one native call (``gnca_rollout_tangent_block``): per step the primal step runs
+        once and the two tangent kernels once per direction.
+
+        ``orthonormalize=True`` (Benettin's method): at every recorded step the block is replaced on the
+        device by Q of its thin QR per sample (``orthonormalize_tangents``' kernels, fp64, fixed order, no
+        host wait) and ``log_r`` [R,B,K] carries the running sums of ``log R_jj``, so
+        ``result.exponents()`` is the finite-time Lyapunov spectrum.  A direction that becomes zero,
+        non-finite or dependent on the earlier ones is dropped: ``-inf`` from that record on, zeros in
+        ``v_final``.  ``orthonormalize=False``: nothing is rescaled, column j is bitwise
+        ``rollout_tangent(x, V[j])`` and ``log_r[:, :, j]`` its ``log_norm``.
+        A sample that ``nsteps`` has finished keeps its block; later records re-factor an orthonormal
+        block, so their contribution to ``log_r`` is 0 within rounding.  The schedule keywords, the taps
+        and the refusals are ``rollout_tangent``'s."""
+        return run_rollout_tangent_block(self, x, V, steps, self.graph, self.hidden_only, every=every,
+                                         record=record, orthonormalize=orthonormalize, fire_rate=fire_rate,
+                                         message_gain=self.message_gain if message_gain is None else message_gain,
+                                         nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                         sample_base=sample_base, offsets=offsets)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
                 min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,

@@ -1028,3 +1028,54 @@ def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormaliz
             v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
     L.check(rc, "gnca_rollout_tangent")
     return x_final, v_final, log_norm
+
+
+# ---------------------------------------------------------------------------------------------
+# A block of K tangents (gnca_tangent_qr / gnca_rollout_tangent_block)
+# ---------------------------------------------------------------------------------------------
+def tangent_qr(v, want_r: bool = True, ws=None):
+    """The thin QR of the block ``v`` [K,B,...] (float32, contiguous, on the GPU), IN PLACE: ``v`` becomes Q.
+    Returns (r float64 [B,K,K] or None, log_diag float64 [B,K], ws); the workspace begins with the Gram
+    partials, float64 [B][nchunk][K(K+1)/2] (include/gnca.h)."""
+    fn = _tangent_entry("gnca_tangent_qr")
+    lib = L.load()
+    K, B = v.shape[0], v.shape[1]
+    n = v[0, 0].numel()
+    if ws is None:
+        nb = lib.gnca_tangent_qr_workspace_bytes(K, B, n)
+        if nb == 0:
+            raise L.GncaError(f"gnca_tangent_qr: no workspace for K={K} B={B} n={n} "
+                              f"(1 <= K <= {L.TANGENT_MAX_DIRS}, B >= 1, n >= 1)")
+        ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+    r = torch.empty(B, K, K, dtype=torch.float64, device=v.device) if want_r else None
+    log_diag = torch.empty(B, K, dtype=torch.float64, device=v.device)
+    rc = fn(K, B, n, v.data_ptr(), _ptr(r), log_diag.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(v.device))
+    L.check(rc, "gnca_tangent_qr")
+    return r, log_diag, ws
+
+
+def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orthonormalize: bool):
+    """(x_final, v_final [K,B,C,H,W], log_r float64 [R,B,K]) of the schedule bound in ``call``."""
+    fn = _tangent_entry("gnca_rollout_tangent_block")
+    lib = L.load()
+    desc, dev = call.desc, x.device
+    K = v.shape[0]
+    a = L.TangentBlockArgs()
+    a.num_dirs = K
+    a.num_records = len(record)
+    arr = (ctypes.c_int32 * max(1, len(record)))(*record)
+    a.record = ctypes.cast(arr, ctypes.c_void_p) if record else None
+    a.flags = L.TBLOCK_ORTHO if orthonormalize else 0
+    log_r = torch.empty(len(record), desc.B, K, dtype=torch.float64, device=dev)
+    a.log_r = log_r.data_ptr() if record else None
+    a.stream = stream_ptr(dev)
+    n = lib.gnca_rollout_tangent_block_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(a))
+    if n == 0:
+        raise L.GncaError(f"unsupported tangent block rollout: K={K} B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    x_final, v_final = torch.empty_like(x), torch.empty_like(v)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
+            v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
+    L.check(rc, "gnca_rollout_tangent_block")
+    return x_final, v_final, log_r

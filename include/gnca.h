@@ -1096,6 +1096,78 @@ int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, cons
                          const gnca_tangent_args* args, const float* x, const float* v, float* x_final,
                          float* v_final, void* ws, size_t ws_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * A block of K tangents, re-orthonormalised on the device (Benettin's method):
+ * the thin QR of a tangent block, and the rollout that carries K directions beside one primal state.
+ * The block is direction-major: v [K][B][n] fp32, n = C*H*W, so direction j is the contiguous
+ * [B,C,H,W] tensor at v + j*B*n that gnca_step_tangent accepts.
+ *
+ * gnca_tangent_qr factors, per sample b independently, V_b = [v_1 .. v_K] (n x K) = Q_b R_b with R_b
+ * upper triangular and a non-negative diagonal, by Cholesky of the fp64 Gram matrix G = V^T V (a
+ * product of two fp32 values is exact in fp64; fixed-order sums, no float atomics):
+ *   for j = 0..K-1:  d_j = G_jj - sum_{i<j} R_ij^2                                  (i ascending)
+ *     d_j positive, finite and > 2^-44 G_jj:  R_jj = sqrt(d_j),
+ *                                             R_jk = (G_jk - sum_{i<j} R_ij R_ik) / R_jj  for k > j
+ *     otherwise column j is DROPPED: row j of R is zero, log R_jj = -inf, Q_j is all zeros and the
+ *     column contributes nothing to later columns (its entries R_ij, i < j, stay as computed).
+ *   Q_j(e) = sum_{i<=j} V_i(e) Rinv_ij   in fp64, i ascending, dropped i skipped, rounded to fp32 once,
+ *   with Rinv the inverse of R on the kept rows and columns and zero elsewhere.
+ * 2^-44: fp32 inputs carry a relative rounding of 2^-24, so a column in the span of the earlier ones
+ * up to that rounding leaves a residual near 2^-48 G_jj; the threshold is 16 times that.  A non-finite
+ * Gram entry drops its column by the same rule.  K > n is served: the surplus columns drop.
+ *   v         [K][B][n], overwritten by Q
+ *   r         [B][K][K] fp64 row-major, zeros below the diagonal, or NULL
+ *   log_diag  [B][K] fp64, log R_jj, or NULL
+ * The workspace begins with the Gram partials, fp64 [B][nchunk][K(K+1)/2], nchunk =
+ * ceil(n / GNCA_TANGENT_QR_CHUNK), entry (i <= j) at j(j+1)/2 + i; their sum over the chunks, in
+ * chunk order, is G.  GNCA_ERR_INVALID before any launch for K outside 1..GNCA_TANGENT_MAX_DIRS,
+ * B < 1, n < 1 or a null v; bitwise reproducible, a sample's results do not depend on the others.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_TANGENT_MAX_DIRS 16
+#define GNCA_TANGENT_QR_CHUNK 4096     /* elements of one sample per Gram workgroup */
+#define GNCA_TBLOCK_ORTHO (1u << 0)    /* replace the block by Q at every recorded step */
+
+typedef struct gnca_tangent_block_args {
+  int32_t num_dirs;        /* K, 1..GNCA_TANGENT_MAX_DIRS                                      */
+  int32_t num_records;     /* R >= 0                                                           */
+  const int32_t* record;   /* HOST [R], strictly increasing, in 1..sched->steps                */
+  uint32_t flags;          /* GNCA_TBLOCK_ORTHO                                                */
+  double* log_r;           /* DEVICE [R][B][K] or NULL when R = 0                              */
+  void* stream;            /* hipStream_t, NULL = the null stream                              */
+} gnca_tangent_block_args;
+
+/* Bytes of device workspace gnca_tangent_qr needs (0 on invalid sizes).  Host-only. */
+size_t gnca_tangent_qr_workspace_bytes(int32_t num_dirs, int32_t B, int64_t n);
+
+int gnca_tangent_qr(int32_t num_dirs, int32_t B, int64_t n, float* v, double* r, double* log_diag, void* ws,
+                    size_t ws_bytes, void* hip_stream);
+
+/* Bytes of device workspace gnca_rollout_tangent_block needs (0 on an invalid or unsupported desc,
+ * schedule or args).  Host-only.  [T][B] masks, one step workspace, two states, 2K tangents, the Gram
+ * partials, Rinv and the carry: apart from the masks it does not grow with T, and it is linear in K. */
+size_t gnca_rollout_tangent_block_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                                  const gnca_tangent_block_args* args);
+
+/*
+ * gnca_rollout_tangent for K directions v [K][B][C][H][W] beside ONE primal state: per step the primal
+ * step and the mask / GroupNorm preparation run once, the two tangent kernels once per direction.
+ * Schedule, fire modes, nsteps / full_steps and support set are gnca_rollout_tangent's, and so are its
+ * refusals (GNCA_SCHED_RECOMPUTE / GNCA_SCHED_CHECKPOINT: GNCA_ERR_INVALID; the zero-padded shift:
+ * GNCA_ERR_UNSUPPORTED, workspace size 0), all before any launch.  x_final is bitwise
+ * gnca_rollout_fwd_f32's.
+ *   without GNCA_TBLOCK_ORTHO  nothing is rescaled: v_final[j] is bitwise gnca_rollout_tangent's v_final
+ *       on v[j], and log_r[r][b][j] bitwise its log_norm[r][b].
+ *   with GNCA_TBLOCK_ORTHO     at every recorded step the block is replaced by gnca_tangent_qr's Q
+ *       (the same kernels), log_r[r][b][j] = log R_jj + carry[b][j] and then carry[b][j] += log R_jj,
+ *       in fp64 and in record order.  A dropped column records -inf, leaves its carry alone and stays
+ *       zero from then on.  log_r[R-1] / record[R-1] is the finite-time Lyapunov spectrum.
+ * A sample that nsteps has finished passes its block through; later records re-factor an already
+ * orthonormal block, so their R is I and the logs are 0 within rounding.  There is no special case.
+ */
+int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                               const gnca_tangent_block_args* args, const float* x, const float* v,
+                               float* x_final, float* v_final, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
