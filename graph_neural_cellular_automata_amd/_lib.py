@@ -240,7 +240,8 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_step_tangent_workspace_bytes", "gnca_step_tangent",
            "gnca_rollout_tangent_workspace_bytes", "gnca_rollout_tangent",
            "gnca_tangent_qr_workspace_bytes", "gnca_tangent_qr",
-           "gnca_rollout_tangent_block_workspace_bytes", "gnca_rollout_tangent_block")
+           "gnca_rollout_tangent_block_workspace_bytes", "gnca_rollout_tangent_block",
+           "gnca_k2_variant")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7

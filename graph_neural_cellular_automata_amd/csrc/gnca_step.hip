@@ -19,6 +19,8 @@
 //                                GroupNorm partials (no atomics: deterministic).
 //   K2  gnca_k2_finalize         GroupNorm (per-sample stats combined in fixed order), tanh*gain,
 //                                residual, post-update alive gate on alpha (3x3 halo) -> x_out.
+//       gnca_k2_finalize_flat    the same on the compact field beside a K1 (the rollout's sub-batch
+//                                pipeline): one thread per 4-cell vector, no LDS, no barrier.
 //
 // MFMA fragment maps (v_mfma_f32_16x16x4_f32, lane l, g = l>>4, col = l&15):
 //   A[16x4]: lane supplies A[l&15][g];  B[4x16]: lane supplies B[g][l&15];
@@ -1339,12 +1341,184 @@ __global__ __launch_bounds__(kThreads) GNCA_K2_ATTR void gnca_k2_finalize(const 
     GNCA_STAMP_END(a.stamps);
     return;
   }
-  // K2's waves issue ahead of the co-resident K1's (the sub-batch pipeline, GNCA_K1_PRIO = 2): K2 is
+  // K2's waves issue ahead of the co-resident K1's (the sub-batch pipeline, GNCA_K1_PRIO = 1): K2 is
   // memory-bound, so it issues its loads at once and then waits, and K1 has the SIMD meanwhile;
   // below K1 it was starved of issue slots and held its CU share longer (headline step 0.512 ->
   // 0.495 ms, profiles/r04_ab_k2_priority.txt)
   __builtin_amdgcn_s_setprio(GNCA_K2_PRIO);
   k2_body<V, COMPACT, CU, ROWS>(a, smem, sh_norm);
+  GNCA_STAMP_END(a.stamps);
+}
+
+// K2 on the compact field without the band structure: one thread per 4-cell vector of a sample,
+// ceil(H W / 4 / 256) workgroups per sample, no LDS and no barrier, so every lane streams from its
+// first instruction and nothing but registers limits how many waves sit beside a K1 workgroup.
+// Only the alpha channel needs neighbours: each thread recomputes the updated alpha over its own
+// 3 x 6 window (fin_alpha on the same inputs as the band kernel's LDS plane: the same bits) and
+// pools it in registers; the window is clamped at the image edge (a duplicate of an in-window
+// value: the same max as the -inf border).  Each wave sums the sample's GroupNorm partials itself
+// (wave_sum2's fixed order: the same mean / rstd bits in every wave); a channel's constants sit on
+// lane c and reach the loop as scalars.  Requires W % 4 == 0, TW % 4 == 0 (a vector never
+// straddles a tile column), nst <= 256 (wave_sum2_regs), no active mask, no attention, no row sums.
+#ifndef GNCA_K2_FLAT_CU
+#define GNCA_K2_FLAT_CU 3   // channels in flight per thread
+#endif
+// Wave priority: K1's groups run at 1 (GNCA_K1_PRIO; only its preparer wave runs at 2, GNCA_PREP_PRIO).
+// Unlike the band kernel (3), the flat K2 must not run above K1's groups: it needs about half of a K1
+// launch's span, so it has slack and K1 is the critical path.  Measured at the headline, interleaved:
+// above K1's groups (3 and 2) 0.481-0.489 ms/step; equal to them (1) and below (0) the same, 0.466-0.478;
+// the band kernel 0.479-0.483.
+#ifndef GNCA_K2_FLAT_PRIO
+#define GNCA_K2_FLAT_PRIO 1
+#endif
+// 8 waves per SIMD = 64 VGPRs: two flat waves per SIMD fit beside the 190-VGPR K1 (a cap at 40 VGPRs
+// spilled at every CU and ran slower)
+template <int V, int CU = GNCA_K2_FLAT_CU>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8))) void gnca_k2_finalize_flat(const K2Args a) {
+  static_assert(V == 4, "one 16-byte cell vector per thread");
+  typedef float vf __attribute__((ext_vector_type(V)));
+  typedef float vfu __attribute__((ext_vector_type(V), aligned(4)));
+  wg_stamp(a.stamps, 0);
+  __builtin_amdgcn_s_setprio(GNCA_K2_FLAT_PRIO);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int C = a.C, H = a.H, W = a.W, HW = H * W;
+  const int nvs = HW / V, nwg = (nvs + kThreads - 1) / kThreads;
+  const int bj = blockIdx.x / nwg, q = (blockIdx.x - bj * nwg) * kThreads + tid;
+  const int b = k2_sample(bj, a.B, a.zigzag);
+  const bool gn = a.use_gn != 0;
+  // the sample's planes behind uniform base pointers, so that a lane addresses them with one 32-bit
+  // offset (the host checks that a sample's state and packed field stay below 2^30 floats)
+  const int TH = a.TH, TW = a.TW, txn = a.tiles_x, NCELL = TH * TW;
+  const float* xb = a.x + (size_t)b * C * HW;
+  float* ob = a.out + (size_t)b * C * HW;
+  const float* xa = xb + 3 * (size_t)HW;
+  const float* da = a.dxa + (size_t)b * HW;
+  const float* dxb = a.dx + (size_t)b * a.tps * C * NCELL;
+  const uint64_t* rmb = a.rmask + (size_t)b * a.tps * TH;
+  const uint32_t* rm32 = reinterpret_cast<const uint32_t*>(rmb);
+  const uint32_t* rpb = a.rpre + (size_t)b * a.tps * TH;
+  if (q - lane < nvs) {   // (a wave with no vector has nothing to do; the branch is wave-uniform)
+    // (1) the sample's GroupNorm partials (lane l: pairs l + 64 j, zeros past nst: wave_sum2_regs, the
+    //     band kernel's bits in every wave) and the affine parameters; without GroupNorm neither is read
+    double sa[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
+    if (gn) {
+      const double* stp = a.stats + (size_t)b * a.nst * 2;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int t = lane + 64 * j, tc = min(t, a.nst - 1);
+        const double pa = stp[2 * tc], pb = stp[2 * tc + 1];
+        sa[j] = t < a.nst ? pa : 0.0;
+        sb[j] = t < a.nst ? pb : 0.0;
+      }
+    }
+    const int lc = lane < C ? lane : 0;
+    const float gam_l = gn ? a.gamma[lc] : 1.f, bet_l = gn ? a.beta[lc] : 0.f;
+
+    // (2) this thread's vector: row i, columns j0 .. j0 + 3 (clamped for the tail lanes, which
+    //     load like the sample's last vector and store nothing), and its own row tables (the
+    //     other channels' unpacking, below)
+    const bool on = q < nvs;
+    const int e = V * (on ? q : nvs - 1);
+    const int i = e / W, j0 = e - i * W;
+    const int tx = j0 / TW, tj = j0 - tx * TW;
+    const int tile1 = (i / TH) * txn + tx, trow1 = tile1 * TH + (i - (i / TH) * TH);
+    const uint64_t m = rmb[trow1];
+    const uint32_t pre1 = rpb[trow1];
+
+    // (3) mean / rstd and the per-channel constants (lane c holds channel c's)
+    float mu = 0.f, rs = 1.f;
+    if (gn) {
+      double t1, t2;
+      wave_sum2_regs(sa, sb, &t1, &t2);
+      fin_mu_rs(t1, t2, (double)C * (double)HW, a.eps, &mu, &rs);
+    }
+    const float g3 = __shfl(gam_l, 3), b3 = __shfl(bet_l, 3);
+    float sc_l, sh_l;
+    fin_consts(gam_l, bet_l, mu, rs, gn, &sc_l, &sh_l);
+    const float g2 = -2.f * a.gain;
+
+    // (4) the updated alpha over the window (rows i-1, i, i+1, columns j0-1 .. j0+4, clamped), its 3x3
+    //     max, the gate and the next step's alive bytes.  The live bit of each window cell comes from
+    //     the 32-bit half of its (row, tile column) rmask entry (a vector's four bits share a half);
+    //     a dead cell's dxa is unwritten: select, not multiply.  The three rows' loads are in flight
+    //     together (one row at a time measured no faster).
+    const int jl = j0 > 0 ? j0 - 1 : j0, jr = j0 + V < W ? j0 + V : j0 + V - 1;
+    const int txl = jl / TW, tjl = jl - txl * TW, txr = jr / TW, tjr = jr - txr * TW;
+    const bool seam_l = txl != tx || (tjl >> 5) != (tj >> 5), seam_r = txr != tx || (tjr >> 5) != (tj >> 5);
+    vf cm, ctr;
+    float ml = -INFINITY, mr = -INFINITY;
+    auto row = [&](int k) {
+      const int r = k == 0 ? (i > 0 ? i - 1 : i) : k == 1 ? i : (i < H - 1 ? i + 1 : i);
+      const int ty = r / TH, trow = ty * txn * TH + (r - ty * TH);   // + tile column * TH
+      const uint32_t wm = rm32[2 * (trow + tx * TH) + (tj >> 5)];
+      uint32_t wml = wm >> (tjl & 31), wmr = wm >> (tjr & 31);
+      if (seam_l) wml = rm32[2 * (trow + txl * TH) + (tjl >> 5)] >> (tjl & 31);
+      if (seam_r) wmr = rm32[2 * (trow + txr * TH) + (tjr >> 5)] >> (tjr & 31);
+      const int rp = r * W;
+      const vf wx = *reinterpret_cast<const vf*>(xa + (rp + j0)), wd = *reinterpret_cast<const vf*>(da + (rp + j0));
+      const float lx = xa[rp + jl], ld = da[rp + jl], rx = xa[rp + jr], rd = da[rp + jr];
+      vf v;
+#pragma unroll
+      for (int c = 0; c < V; ++c)
+        v[c] = fin_alpha(wx[c], ((wm >> ((tj & 31) + c)) & 1u) ? wd[c] : 0.f, mu, rs, g3, b3, a.gain, gn);
+      const float vl = fin_alpha(lx, (wml & 1u) ? ld : 0.f, mu, rs, g3, b3, a.gain, gn);
+      const float vr = fin_alpha(rx, (wmr & 1u) ? rd : 0.f, mu, rs, g3, b3, a.gain, gn);
+      if (k == 1) ctr = v;
+#pragma unroll
+      for (int c = 0; c < V; ++c) cm[c] = k == 0 ? v[c] : fmaxf(cm[c], v[c]);
+      ml = fmaxf(ml, vl);
+      mr = fmaxf(mr, vr);
+    };
+    row(0); row(1); row(2);
+    if (on) {
+      vf v;
+      uint32_t bytes = 0;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float left = c == 0 ? ml : cm[c - 1], right = c == V - 1 ? mr : cm[c + 1];
+        const float mx = fmaxf(fmaxf(left, cm[c]), right);
+        v[c] = ctr[c] * (mx > a.thr ? 1.f : 0.f);
+        bytes |= (uint32_t)((mx > a.thr ? 1 : 0) | (mx > a.gthr ? 2 : 0)) << (8 * c);
+      }
+      *reinterpret_cast<vf*>(ob + 3 * (size_t)HW + e) = v;
+      if (a.alive_out) *reinterpret_cast<uint32_t*>(a.alive_out + (size_t)b * HW + e) = bytes;
+
+      // (5) the other channels: the vector's live cells are contiguous in the packed field (the band
+      //     kernel's unpacking: one dword-aligned load per channel, placed by rank; the over-read of
+      //     up to V-1 floats stays inside the workspace), CU channels in flight
+      const uint32_t bits = (uint32_t)(m >> tj) & ((1u << V) - 1u);
+      const int so = tile1 * C * NCELL + (int)pre1 + __popcll(m & ((1ull << tj) - 1ull));
+      int rk[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) rk[k] = ((bits >> k) & 1u) ? __popc(bits & ((1u << k) - 1u)) : -1;
+      for (int n0 = 0; n0 < C - 1; n0 += CU) {   // the n-th non-alpha channel: c = n + (n >= 3)
+        vf xq[CU], fq[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) {
+          if (n0 + u >= C - 1) continue;
+          const int c = n0 + u + (n0 + u >= 3 ? 1 : 0);
+          xq[u] = *reinterpret_cast<const vf*>(xb + (size_t)c * HW + e);
+          fq[u] = *reinterpret_cast<const vfu*>(dxb + (size_t)c * NCELL + so);
+        }
+#pragma unroll
+        for (int u = 0; u < CU; ++u) {
+          if (n0 + u >= C - 1) continue;
+          const int c = n0 + u + (n0 + u >= 3 ? 1 : 0);
+          const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc_l), c));
+          const float sh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sh_l), c));
+          vf v2;
+#pragma unroll
+          for (int k = 0; k < V; ++k) {
+            float d = 0.f;
+#pragma unroll
+            for (int r = 0; r <= k; ++r) d = rk[k] == r ? fq[u][r] : d;
+            v2[k] = k2_update(xq[u][k], d, sc, sh, a.gain, g2);
+          }
+          *reinterpret_cast<vf*>(ob + (size_t)c * HW + e) = v2;
+        }
+      }
+    }
+  }
   GNCA_STAMP_END(a.stamps);
 }
 
@@ -2109,6 +2283,24 @@ static FieldSet field_set(const Plan& P, char* wsb, int set) {
           reinterpret_cast<float*>(wsb + P.off_dxa2)};
 }
 
+// Which K2 finishes a step on the compact field: the flat kernel (gnca_k2_finalize_flat) where its
+// mapping holds (whole 4-cell vectors inside one tile column, the partials in one wave pass) and the
+// plan has no fused row sums (rows: the zero-padded shift keeps the band kernel's ROWS instance).
+// co: beside another sub-batch stream's K1 (k2_co).  Alone on the chip (one-stream rollouts, the
+// fold's last K2) GNCA_K2_FLAT_ALONE decides (DESIGN.md A.0 has the measurement).
+#ifndef GNCA_K2_FLAT
+#define GNCA_K2_FLAT 1   // measurement builds: 0 = the band kernel everywhere
+#endif
+#ifndef GNCA_K2_FLAT_ALONE
+#define GNCA_K2_FLAT_ALONE 0
+#endif
+static bool k2_flat_ok(const gnca_step_desc* d, const Plan& P, bool rows, bool co) {
+  if (!GNCA_K2_FLAT || rows || (d->W & 3) != 0 || P.TW <= 0 || (P.TW & 3) != 0 || P.tps * P.ppt > 256) return false;
+  // (a lane addresses its sample's state and packed field with 32-bit offsets)
+  if ((size_t)d->C * d->H * d->W >= ((size_t)1 << 30) || (size_t)P.tps * d->C * P.TH * P.TW >= ((size_t)1 << 30)) return false;
+  return co || GNCA_K2_FLAT_ALONE;
+}
+
 // alive_in / alive_out (rollout only): the previous step's K2 hands this step's K1 its pre-update
 // masks as bytes, so K1 skips the alpha halo and the 3x3 max-pools.  set: the update
 // field set (the fold rollout alternates sets 0 / 1 by step parity; everything else uses 0).
@@ -2211,6 +2403,17 @@ static int step_impl(const gnca_step_desc* d, const gnca_weights* w, const float
     k2.TH = P.TH;
     k2.TW = P.TW;
     k2.tiles_x = P.tiles_x;
+  }
+  if (compact && k2_flat_ok(d, P, rows_k2, k2_co)) {
+    // the flat finalize: one thread per 4-cell vector, no LDS (gnca_k2_finalize_flat)
+    const long nwg = ((long)d->H * d->W / 4 + kThreads - 1) / kThreads;
+    const long grid = nwg * d->B;
+    if (stamps) {
+      if (grid > stamp_cap) return GNCA_ERR_INVALID;
+      k2.stamps = stamps + 2 * (size_t)stamp_cap;
+    }
+    hipLaunchKernelGGL((gnca_k2_finalize_flat<4>), dim3((unsigned)grid), dim3(kThreads), 0, st, k2);
+    return check_launch();
   }
   if (stamps) {
     if ((compact ? P.total2_c : P.total2) > stamp_cap) return GNCA_ERR_INVALID;
@@ -2328,7 +2531,9 @@ static int rollout_subs(const gnca_step_desc* d) {
     Plan Q;
     if (!make_plan(&sd, false, &Q) || Q.var != P.var || !Q.compact_ok) return 1;
 #ifndef GNCA_SUBS_ANY
-    if (Q.lds1 + Q.lds2_c + 512 > (size_t)max_lds_bytes()) return 1;   // K2's static LDS + margin
+    // the band K2 shares the CU's LDS with K1 (+ its static LDS and a margin); the flat K2 uses none
+    const bool rows = Q.need_k0 && sd.W / ((sd.W & 3) == 0 ? 4 : 1) <= 32;
+    if (!k2_flat_ok(&sd, Q, rows, true) && Q.lds1 + Q.lds2_c + 512 > (size_t)max_lds_bytes()) return 1;
 #endif
   }
   return kRolloutSubs;
@@ -2418,6 +2623,33 @@ int gnca_k1_variant(const gnca_step_desc* desc, char* name, int32_t n, int32_t* 
              v->KU, v->NT);
   if (arith) *arith = (v->split ? 1 : 0) | (P.compact_ok ? 2 : 0) | (rollout_subs(desc) > 1 ? 4 : 0) |
                       (P.fold_ok ? 8 : 0) | (P.fold_any ? 16 : 0);
+  return GNCA_OK;
+}
+
+int gnca_k2_variant(const gnca_step_desc* desc, int32_t co, char* name, int32_t n) {
+  if (!name || n <= 0 || !desc || co < -1 || co > 1) return GNCA_ERR_INVALID;
+  gnca_step_desc dt = *desc;
+  if (co >= 0) dt.flags &= ~GNCA_ATTENTION;   // as rollout_impl
+  if (co == 1) {
+    const int nsub = rollout_subs(&dt);
+    if (nsub < 2) return GNCA_ERR_INVALID;
+    gnca_step_desc d0;
+    int b0;
+    sub_desc(&dt, 0, nsub, &d0, &b0);
+    dt = d0;
+  }
+  Plan P;
+  if (!make_plan(&dt, false, &P)) return GNCA_ERR_INVALID;
+  // step_impl's selection
+  const int V = (dt.W & 3) == 0 ? 4 : 1;
+  const bool compact = co >= 0 && P.compact_ok;
+  const bool rows = P.need_k0 && compact && dt.W / V <= 32;
+  if (compact && k2_flat_ok(&dt, P, rows, co == 1))
+    snprintf(name, (size_t)n, "gnca_k2_finalize_flat<4,%d>", GNCA_K2_FLAT_CU);
+  else
+    snprintf(name, (size_t)n, "gnca_k2_finalize<%d,%s,%d,%s>", V, compact ? "true" : "false",
+             !compact ? GNCA_K2_CU : rows ? GNCA_K2_CU_ROWS : co == 1 ? GNCA_K2_CU : GNCA_K2_CU_ALONE,
+             rows ? "true" : "false");
   return GNCA_OK;
 }
 

@@ -152,6 +152,19 @@ def bb_variant(desc: L.StepDesc) -> str:
     return buf.value.decode()
 
 
+def k2_variant(desc: L.StepDesc, co: int = 0) -> str:
+    """The K2 (finalize) kernel a step of ``desc`` launches (gnca_k2_variant, host-only):
+    "gnca_k2_finalize_flat<V,CU>" or the band kernel "gnca_k2_finalize<V,COMPACT,CU,ROWS>".  ``co``: 1 = a
+    step of a rollout's sub-batch pipeline (K2 beside the other sub-batch's K1), 0 = a rollout step with
+    K2 alone on the chip, -1 = a single (or masked) step."""
+    lib = L.load()
+    lib.gnca_k2_variant.restype = ctypes.c_int
+    lib.gnca_k2_variant.argtypes = [ctypes.POINTER(L.StepDesc), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]
+    buf = ctypes.create_string_buffer(128)
+    L.check(lib.gnca_k2_variant(ctypes.byref(desc), int(co), buf, 128), "gnca_k2_variant")
+    return buf.value.decode()
+
+
 def rollout_compact(desc: L.StepDesc) -> bool:
     """True when a rollout of ``desc``'s shape runs on the compact update field (K1 packs the live
     cells' dx per tile, K2 unpacks them: GNCA_PHASE_COMPACT)."""

@@ -147,6 +147,15 @@ size_t gnca_workspace_bytes(const gnca_step_desc* desc);
  * Returns GNCA_OK or GNCA_ERR_INVALID. */
 int gnca_k1_variant(const gnca_step_desc* desc, char* name, int32_t n, int32_t* arith);
 
+/* Measurement: the K2 (finalize) kernel a step of `desc` launches, as "name<template args>":
+ * "gnca_k2_finalize_flat<V,CU>" (one thread per V-cell vector, no LDS; compact update field only) or
+ * the band kernel "gnca_k2_finalize<V,COMPACT,CU,ROWS>".  co = 1: a step of a rollout's sub-batch
+ * pipeline, K2 beside the other sub-batch's K1 (GNCA_ERR_INVALID when a rollout of this shape runs
+ * on one stream); co = 0: a rollout step with K2 alone on the chip (one-stream rollouts, the last K2
+ * of a fold); co = -1: a single step (gnca_step_f32, gnca_step_masked_f32: the dense update field).
+ * Host-only.  Returns GNCA_OK or GNCA_ERR_INVALID. */
+int gnca_k2_variant(const gnca_step_desc* desc, int32_t co, char* name, int32_t n);
+
 /*
  * One CA step: x_out = step(x).  Out-of-place (x_out must not alias x), like the reference.
  *   fire:  NULL, or [B,1,H,W] fp32 uniforms (GNCA_FIRE_RAND_F32) / uint8 mask (GNCA_FIRE_MASK_U8)
