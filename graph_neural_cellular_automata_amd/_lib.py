@@ -241,7 +241,8 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_rollout_tangent_workspace_bytes", "gnca_rollout_tangent",
            "gnca_tangent_qr_workspace_bytes", "gnca_tangent_qr",
            "gnca_rollout_tangent_block_workspace_bytes", "gnca_rollout_tangent_block",
-           "gnca_k2_variant")
+           "gnca_k2_variant",
+           "gnca_step_tangent_params", "gnca_rollout_tangent_params", "gnca_rollout_tangent_block_params")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -441,6 +442,18 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_tangent_block.restype = ctypes.c_int
             lib.gnca_rollout_tangent_block.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(Weights),
                                                        ctypes.POINTER(RolloutSched), tb, vp, vp, vp, vp, vp, sz]
+        if hasattr(lib, "gnca_step_tangent_params"):   # (likewise); dw is a Weights, or an array of K for the block
+            wp = ctypes.POINTER(Weights)
+            lib.gnca_step_tangent_params.restype = ctypes.c_int
+            lib.gnca_step_tangent_params.argtypes = [ctypes.POINTER(StepDesc), wp, wp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                                     vp]
+            lib.gnca_rollout_tangent_params.restype = ctypes.c_int
+            lib.gnca_rollout_tangent_params.argtypes = [ctypes.POINTER(StepDesc), wp, wp, ctypes.POINTER(RolloutSched),
+                                                        ctypes.POINTER(TangentArgs), vp, vp, vp, vp, vp, sz]
+            lib.gnca_rollout_tangent_block_params.restype = ctypes.c_int
+            lib.gnca_rollout_tangent_block_params.argtypes = [ctypes.POINTER(StepDesc), wp, wp,
+                                                              ctypes.POINTER(RolloutSched),
+                                                              ctypes.POINTER(TangentBlockArgs), vp, vp, vp, vp, vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -14,6 +14,8 @@
 //   TQ  gnca_t_gram / gnca_t_factor / gnca_t_apply     the thin QR of a block of K tangents (gnca_tangent_qr), which
 //                        gnca_rollout_tangent_block runs at a tapped step; that rollout runs
 //                        the primal step and T0 once per step and TA, TB once per direction
+//   The *_params entry points carry a direction of the WEIGHTS beside v: TA's PT instances
+//   add dW1 y, db1, dW2 relu(hpre), dWm s_x and dbm cnt from a second image set in LDS, TB adds dgamma xhat + dbeta.
 //
 // TA is persistent.  A wave owns 32 consecutive cells of one sample: the cells are the columns of
 // v_mfma_f32_32x32x2_f32 tiles, so each of the 64 lanes holds one cell (lane & 31) and one of the two
@@ -126,14 +128,25 @@ struct TAArgs {
   uint64_t seed;
   int64_t rng_step, sample_base;
   int8_t off[2 * GNCA_MAX_OFFSETS];
+  // the parameter direction (PT instances only; NULL = a zero direction for that tensor)
+  const float *dw1, *db1, *dw2, *dwm, *dbm;
+  int npass;              // hidden passes of a PT launch: 2 where both image sets of all hidden rows do not fit
 };
 
-template <int NB>   // 32-row hidden blocks per slice
+constexpr int kPassRows = 128;   // hidden rows of one pass of a pass-staged PT launch (one NB = 4 slice)
+
+// PT: beside v, a direction (dW1, db1, dW2, dWm, dbm) of the weights.  Its images sit
+// behind the first set in the same order, and every term is one more MFMA into an accumulator that exists:
+// dW1 y into accv, dW2 relu(hpre) into accu, dWm s_x into accd.  With npass == 2 the W1 / b1 / W2 images of
+// both sets hold 128 hidden rows at a time: the pass loop is outside the tile loop, a wave visits the same
+// tiles on the same lanes in both passes and parks accu in its own cells of ud between them.
+template <int NB, bool PT>   // 32-row hidden blocks per slice
 __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int C = a.C, H = a.H, W = a.W, Hd = a.hidden;
-  const TLds L = t_lds(C, Hd, 32 * NB);
+  const int npass = PT ? a.npass : 1;
+  const TLds L = t_lds(C, (PT && npass > 1) ? kPassRows : Hd, 32 * NB);
   const int HP = L.HP, CPe = L.CPe;
   float* w1s = smem + L.w1;
   float* b1s = smem + L.b1;
@@ -141,23 +154,54 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
   float* wms = smem + L.wm;
   float* bms = smem + L.bm;
   float* wps = smem + L.wp;
+  float* dset = smem + L.total;   // (PT) the second image set, at the first set's offsets
   const bool msg = (a.flags & kTMsg) != 0, gn = (a.flags & kTGN) != 0;
+  // PT: the hidden passes, a backward jump at the end of the kernel (PT = false has no such loop around its tiles)
+  int pass = 0;
+next_pass:
+  const int h0 = PT ? pass * HP : 0;   // the first hidden row of this pass's images
+  const bool last = !PT || pass == npass - 1;
+  if constexpr (PT) {
+    if (pass > 0) __syncthreads();   // every wave is done with the previous pass's images
+  }
   // weight images
   lds_fill<kThreads, 8>(w1s, 3 * CPe * HP, tid, [&](int idx) {
-    const int kk = idx / HP, hid = idx - kk * HP, f = kk / CPe, c = kk - f * CPe;
+    const int kk = idx / HP, hid = h0 + idx - kk * HP, f = kk / CPe, c = kk - f * CPe;
     return (c < C && hid < Hd) ? a.w1[(size_t)hid * 3 * C + f * C + c] : 0.f;
   });
-  lds_fill<kThreads, 4>(b1s, HP, tid, [&](int idx) { return idx < Hd ? a.b1[idx] : 0.f; });
+  lds_fill<kThreads, 4>(b1s, HP, tid, [&](int idx) { return h0 + idx < Hd ? a.b1[h0 + idx] : 0.f; });
   lds_fill<kThreads, 8>(w2s, HP * 32, tid, [&](int idx) {
-    const int hid = idx >> 5, co = idx & 31;
+    const int hid = h0 + (idx >> 5), co = idx & 31;
     return (co < C && hid < Hd) ? a.w2[(size_t)co * Hd + hid] : 0.f;
   });
-  lds_fill<kThreads, 4>(wms, CPe * 32, tid, [&](int idx) {
-    const int ci = idx >> 5, co = idx & 31;
-    return (msg && ci < C && co < C) ? a.wm[co * C + ci] : 0.f;
-  });
-  lds_fill<kThreads, 1>(bms, 32, tid, [&](int idx) { return (msg && idx < C) ? a.bm[idx] : 0.f; });
-  lds_fill<kThreads, 4>(wps, 27 * CPe, tid, [&](int idx) { return idx < 27 * C ? a.perc[idx] : 0.f; });
+  if (!PT || pass == 0) {
+    lds_fill<kThreads, 4>(wms, CPe * 32, tid, [&](int idx) {
+      const int ci = idx >> 5, co = idx & 31;
+      return (msg && ci < C && co < C) ? a.wm[co * C + ci] : 0.f;
+    });
+    lds_fill<kThreads, 1>(bms, 32, tid, [&](int idx) { return (msg && idx < C) ? a.bm[idx] : 0.f; });
+    lds_fill<kThreads, 4>(wps, 27 * CPe, tid, [&](int idx) { return idx < 27 * C ? a.perc[idx] : 0.f; });
+  }
+  if constexpr (PT) {
+    lds_fill<kThreads, 8>(dset + L.w1, 3 * CPe * HP, tid, [&](int idx) {
+      const int kk = idx / HP, hid = h0 + idx - kk * HP, f = kk / CPe, c = kk - f * CPe;
+      return (a.dw1 && c < C && hid < Hd) ? a.dw1[(size_t)hid * 3 * C + f * C + c] : 0.f;
+    });
+    lds_fill<kThreads, 4>(dset + L.b1, HP, tid,
+                          [&](int idx) { return (a.db1 && h0 + idx < Hd) ? a.db1[h0 + idx] : 0.f; });
+    lds_fill<kThreads, 8>(dset + L.w2, HP * 32, tid, [&](int idx) {
+      const int hid = h0 + (idx >> 5), co = idx & 31;
+      return (a.dw2 && co < C && hid < Hd) ? a.dw2[(size_t)co * Hd + hid] : 0.f;
+    });
+    if (pass == 0) {
+      lds_fill<kThreads, 4>(dset + L.wm, CPe * 32, tid, [&](int idx) {
+        const int ci = idx >> 5, co = idx & 31;
+        return (msg && a.dwm && ci < C && co < C) ? a.dwm[co * C + ci] : 0.f;
+      });
+      lds_fill<kThreads, 1>(dset + L.bm, 32, tid,
+                            [&](int idx) { return (msg && a.dbm && idx < C) ? a.dbm[idx] : 0.f; });
+    }
+  }
   __syncthreads();
 
   const int col = lane & 31, h = lane >> 5;
@@ -176,6 +220,9 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
     float* udb = a.ud + (size_t)b * C * sHW;
     double* outp = a.part + ((size_t)b * a.ntile + tile) * 2;
     if (__ballot(live) == 0ull) {   // nothing fires in this tile: u' = 0 (wave-uniform branch)
+      if constexpr (PT) {
+        if (!last) continue;   // (the last pass stores the zeros)
+      }
       if (valid)
         for (int c = h; c < C; c += 2) udb[(size_t)c * sHW + cell] = 0.f;
       if (lane == 0) {
@@ -200,6 +247,16 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
     f16v accu;
 #pragma unroll
     for (int r = 0; r < 16; ++r) accu[r] = 0.f;
+    if constexpr (PT) {
+      if (pass > 0) {   // the earlier passes' sum, parked by this lane in its own cells
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c = acc_row(r, h);
+          const float p = udb[(size_t)min(c, C - 1) * sHW + (valid ? cell : 0)];
+          accu[r] = (c < C && valid) ? p : 0.f;   // (a lane without a cell or channel parked nothing)
+        }
+      }
+    }
     for (int hb = 0; hb < HP; hb += 32 * NB) {
       f16v accy[NB], accv[NB];
 #pragma unroll
@@ -246,6 +303,8 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
             const float wa = wrow[32 * nb];
             accy[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, y, accy[nb], 0, 0, 0);
             accv[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, yd, accv[nb], 0, 0, 0);
+            if constexpr (PT)   // dW1 y: the same y, another A fragment
+              accv[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[L.total + 32 * nb], y, accv[nb], 0, 0, 0);
           }
         }
       };
@@ -266,9 +325,26 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int hid = hb + 32 * nb + acc_row(r, h);
-          const float hd = (accy[nb][r] + b1s[hid]) > 0.f ? accv[nb][r] : 0.f;
-          accu = __builtin_amdgcn_mfma_f32_32x32x2f32(w2s[hid * 32 + col], hd, accu, 0, 0, 0);
+          if constexpr (PT) {   // h' gains db1, and u' gains dW2 relu(hpre)
+            const float hpre = accy[nb][r] + b1s[hid];
+            const float hd = hpre > 0.f ? accv[nb][r] + dset[L.b1 + hid] : 0.f;
+            accu = __builtin_amdgcn_mfma_f32_32x32x2f32(w2s[hid * 32 + col], hd, accu, 0, 0, 0);
+            accu = __builtin_amdgcn_mfma_f32_32x32x2f32(dset[L.w2 + hid * 32 + col], fmaxf(hpre, 0.f), accu, 0, 0, 0);
+          } else {
+            const float hd = (accy[nb][r] + b1s[hid]) > 0.f ? accv[nb][r] : 0.f;
+            accu = __builtin_amdgcn_mfma_f32_32x32x2f32(w2s[hid * 32 + col], hd, accu, 0, 0, 0);
+          }
         }
+    }
+    if constexpr (PT) {
+      if (!last) {   // park the partial sum; the message, the masks, the store and the partials are the last pass's
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c = acc_row(r, h);
+          if (c < C && valid) udb[(size_t)c * sHW + cell] = accu[r];
+        }
+        continue;
+      }
     }
     // the message and its tangent: Wm (1/k sum_o shift_o(A_send z)) for z = x and z = v
     f16v accm, accd;
@@ -337,6 +413,10 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
           const float wa = c < CPe ? wms[c * 32 + col] : 0.f;
           accm = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, gx[u] * a.invk, accm, 0, 0, 0);
           accd = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, gv[u] * a.invk, accd, 0, 0, 0);
+          if constexpr (PT) {   // dWm s_x
+            const float dwa = c < CPe ? dset[L.wm + c * 32 + col] : 0.f;
+            accd = __builtin_amdgcn_mfma_f32_32x32x2f32(dwa, gx[u] * a.invk, accd, 0, 0, 0);
+          }
         }
       }
     }
@@ -361,8 +441,27 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
       const bool ok = c < C && valid;
       float u = accu[r];
       if (msg) {
-        const float tm = tanhf(accm[r] + bms[min(c, 31)] * cnt);
-        u += (honly && c < 4) ? 0.f : a.message_gain * (1.f - tm * tm) * accd[r];
+        if constexpr (PT) {
+          // the PT = false instance's roundings, spelled out (its compiler-chosen contractions: an FMA for m and
+          // for 1 - tm^2, the gain's product rounded, and the sum an FMA except on the four registers whose
+          // channel can be below 4, where the hidden-only select sits between product and sum), so that a zero
+          // direction gives its bits whatever the vectoriser makes of this instance; dbm cnt joins accd in one
+          // FMA, exact for dbm = 0
+#pragma clang fp contract(off)
+          const float tm = tanhf(fmaf(bms[min(c, 31)], cnt, accm[r]));
+          const float om = fmaf(-tm, tm, 1.f);
+          const float md = fmaf(dset[L.bm + min(c, 31)], cnt, accd[r]);
+          const float gm = a.message_gain * om;
+          if (r >= 4) {   // (c >= 8: never zeroed)
+            u = fmaf(md, gm, u);
+          } else {
+            const float mt = md * gm;
+            u += (honly && c < 4) ? 0.f : mt;
+          }
+        } else {
+          const float tm = tanhf(accm[r] + bms[min(c, 31)] * cnt);
+          u += (honly && c < 4) ? 0.f : a.message_gain * (1.f - tm * tm) * accd[r];
+        }
       }
       u = (live && ok) ? u : 0.f;
       if (ok) udb[(size_t)c * sHW + cell] = u;
@@ -381,6 +480,9 @@ __global__ __launch_bounds__(kThreads) void gnca_t_mlp(const TAArgs a) {
       }
     }
   }
+  if constexpr (PT) {
+    if (++pass < npass) goto next_pass;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -394,6 +496,7 @@ struct TBArgs {
   int B, C, H, W, ntile;
   float gain, thr;
   int use_gn;
+  const float *dgamma, *dbeta;   // the direction of norm.weight / norm.bias (NULL = none)
 };
 
 __global__ __launch_bounds__(kThreads) void gnca_t_finalize(const TBArgs a) {
@@ -456,6 +559,8 @@ __global__ __launch_bounds__(kThreads) void gnca_t_finalize(const TBArgs a) {
       const float gc = a.gamma[c], xh = (d - mu) * rs;
       xn = xh * gc + a.beta[c];
       un = gc * rs * (u - mu_u - xh * mu_ux);
+      // the direction of the affine part, at every cell (GroupNorm runs on the masked field)
+      if (a.dgamma || a.dbeta) un += (a.dgamma ? a.dgamma[c] : 0.f) * xh + (a.dbeta ? a.dbeta[c] : 0.f);
     }
     const float t = tanhf(xn);
     float o = vv + a.gain * (1.f - t * t) * un;
@@ -770,11 +875,18 @@ bool tan_sched_bytes(const gnca_step_desc* d, const gnca_rollout_sched* s, size_
   return true;
 }
 
-template <int NB>
+// LDS floats of a PT launch: the second image set (no second perception bank) behind the first
+inline int t_lds_pt(const TLds& L) { return L.total + L.wp; }
+
+// the passes of a PT launch: both image sets of every class up to 128 hidden rows fit the CU's 160 KiB (p31: 140.6
+// KiB); the hidden > 128 classes (13 <= C <= 16, up to 167.9 KiB in one piece) take 128 rows at a time
+inline int t_passes(int hidden) { return hidden <= kPassRows ? 1 : (hidden + kPassRows - 1) / kPassRows; }
+
+template <int NB, bool PT>
 int launch_ta(const TAArgs& a, int C, int hidden, hipStream_t st) {
-  const TLds L = t_lds(C, hidden, 32 * NB);
-  const size_t lds = (size_t)L.total * sizeof(float);
-  auto fn = gnca_t_mlp<NB>;
+  const TLds L = t_lds(C, (PT && a.npass > 1) ? kPassRows : hidden, 32 * NB);
+  const size_t lds = (size_t)(PT ? t_lds_pt(L) : L.total) * sizeof(float);
+  auto fn = gnca_t_mlp<NB, PT>;
   // the dynamic-LDS attribute and the resident workgroups per CU (registers and LDS decide), set and asked
   // once per (device, LDS size)
   static std::mutex mu;
@@ -825,9 +937,10 @@ int step_tangent_primal(const gnca_step_desc* desc, const gnca_weights* w, const
 }
 
 // v -> v_out through the step whose primal part has just run in `ws` (x, x_out, fire, active as passed there)
-int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
-                     const uint8_t* active, const float* v, const float* x_out, float* v_out, void* ws,
-                     hipStream_t st) {
+// dw: the parameter direction carried beside v (gnca_step_tangent_params), or NULL: the state tangent alone
+int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw, const float* x,
+                     const void* fire, const uint8_t* active, const float* v, const float* x_out, float* v_out,
+                     void* ws, hipStream_t st) {
   gnca_step_desc d = *desc;
   d.flags &= ~GNCA_ATTENTION;
   TanLayout T;
@@ -855,8 +968,15 @@ int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const fl
     a.invk = a.k > 0 ? (float)(1.0 / (double)a.k) : 0.f;
     a.seed = d.rng_seed; a.rng_step = d.rng_step; a.sample_base = d.sample_base;
     for (int o = 0; o < 2 * a.k; ++o) a.off[o] = d.offsets[o];
-    rc = T.NB == 1 ? launch_ta<1>(a, C, d.hidden, st)
-                   : T.NB == 2 ? launch_ta<2>(a, C, d.hidden, st) : launch_ta<4>(a, C, d.hidden, st);
+    if (dw) {
+      a.dw1 = dw->w1; a.db1 = dw->b1; a.dw2 = dw->w2; a.dwm = dw->wm; a.dbm = dw->bm;
+      a.npass = t_passes(d.hidden);
+      rc = T.NB == 1 ? launch_ta<1, true>(a, C, d.hidden, st)
+                     : T.NB == 2 ? launch_ta<2, true>(a, C, d.hidden, st) : launch_ta<4, true>(a, C, d.hidden, st);
+    } else {
+      rc = T.NB == 1 ? launch_ta<1, false>(a, C, d.hidden, st)
+                     : T.NB == 2 ? launch_ta<2, false>(a, C, d.hidden, st) : launch_ta<4, false>(a, C, d.hidden, st);
+    }
     if (rc != GNCA_OK) return rc;
   }
   {
@@ -866,6 +986,10 @@ int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const fl
     a.part = part; a.active = active; a.v_out = v_out;
     a.B = B; a.C = C; a.H = H; a.W = W; a.ntile = T.ntile;
     a.gain = d.update_gain; a.thr = d.alpha_thr; a.use_gn = T.gn ? 1 : 0;
+    if (dw && T.gn) {
+      a.dgamma = dw->gn_weight;
+      a.dbeta = dw->gn_bias;
+    }
     hipLaunchKernelGGL(gnca_t_finalize, dim3((unsigned)ncb, (unsigned)B), dim3(kThreads), 0, st, a);
     if ((rc = t_check()) != GNCA_OK) return rc;
   }
@@ -873,12 +997,22 @@ int step_tangent_dir(const gnca_step_desc* desc, const gnca_weights* w, const fl
 }
 
 // the body of gnca_step_tangent and of gnca_rollout_tangent's steps
-int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
-                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
-                      hipStream_t st) {
+int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw, const float* x,
+                      const void* fire, const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws,
+                      size_t ws_bytes, hipStream_t st) {
   const int rc = step_tangent_primal(desc, w, x, fire, active, x_out, ws, ws_bytes, st);
   if (rc != GNCA_OK) return rc;
-  return step_tangent_dir(desc, w, x, fire, active, v, x_out, v_out, ws, st);
+  return step_tangent_dir(desc, w, dw, x, fire, active, v, x_out, v_out, ws, st);
+}
+
+// a tensor of the direction dw[0..K) that is one of the outputs
+bool dir_aliases(const gnca_weights* dw, int K, const void* o1, const void* o2) {
+  for (int j = 0; j < K; ++j) {
+    const float* t[] = {dw[j].w1, dw[j].b1, dw[j].w2, dw[j].gn_weight, dw[j].gn_bias, dw[j].wm, dw[j].bm};
+    for (const float* p : t)
+      if (p && (p == o1 || p == o2)) return true;
+  }
+  return false;
 }
 
 bool distinct(const void* const* p, int n) {
@@ -1017,19 +1151,34 @@ size_t gnca_step_tangent_workspace_bytes(const gnca_step_desc* desc) {
   return tan_layout(desc, &T) ? T.bytes : 0;
 }
 
-int gnca_step_tangent(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
-                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
-                      void* hip_stream) {
+// the body of gnca_step_tangent (dw == NULL) and of gnca_step_tangent_params
+static int step_tangent_entry(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                              const float* x, const void* fire, const uint8_t* active, const float* v, float* x_out,
+                              float* v_out, void* ws, size_t ws_bytes, void* hip_stream) {
   if (!desc || !w || !x || !v || !x_out || !v_out) return GNCA_ERR_INVALID;
   const void* ptrs[] = {x, x_out, v_out};
   const void* ptrs2[] = {v, x_out, v_out};
   if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
+  if (dw && dir_aliases(dw, 1, x_out, v_out)) return GNCA_ERR_INVALID;
   if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
   TanLayout T;
   if (!tan_layout(desc, &T)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   StreamDeviceGuard dg(st);
-  return step_tangent_impl(desc, w, x, fire, active, v, x_out, v_out, ws, ws_bytes, st);
+  return step_tangent_impl(desc, w, dw, x, fire, active, v, x_out, v_out, ws, ws_bytes, st);
+}
+
+int gnca_step_tangent(const gnca_step_desc* desc, const gnca_weights* w, const float* x, const void* fire,
+                      const uint8_t* active, const float* v, float* x_out, float* v_out, void* ws, size_t ws_bytes,
+                      void* hip_stream) {
+  return step_tangent_entry(desc, w, nullptr, x, fire, active, v, x_out, v_out, ws, ws_bytes, hip_stream);
+}
+
+int gnca_step_tangent_params(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                             const float* x, const void* fire, const uint8_t* active, const float* v, float* x_out,
+                             float* v_out, void* ws, size_t ws_bytes, void* hip_stream) {
+  if (!dw) return GNCA_ERR_INVALID;
+  return step_tangent_entry(desc, w, dw, x, fire, active, v, x_out, v_out, ws, ws_bytes, hip_stream);
 }
 
 size_t gnca_rollout_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
@@ -1039,13 +1188,17 @@ size_t gnca_rollout_tangent_workspace_bytes(const gnca_step_desc* desc, const gn
   return roll_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
 }
 
-int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
-                         const gnca_tangent_args* args, const float* x, const float* v, float* x_final,
-                         float* v_final, void* ws, size_t ws_bytes) {
+// the body of gnca_rollout_tangent (dw == NULL) and of gnca_rollout_tangent_params
+static int rollout_tangent_entry(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                 const gnca_rollout_sched* sched, const gnca_tangent_args* args, const float* x,
+                                 const float* v, float* x_final, float* v_final, void* ws, size_t ws_bytes) {
   if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
   const void* ptrs[] = {x, x_final, v_final};
   const void* ptrs2[] = {v, x_final, v_final};
   if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
+  if (dw && dir_aliases(dw, 1, x_final, v_final)) return GNCA_ERR_INVALID;
+  // rescaling v alone breaks linearity in the pair (v, dtheta)
+  if (dw && (args->flags & GNCA_TANGENT_RENORM)) return GNCA_ERR_INVALID;
   if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
   if (!sched_ok(desc, sched) || !records_ok(sched, args)) return GNCA_ERR_INVALID;
   if (args->num_records > 0 && !args->log_norm) return GNCA_ERR_INVALID;
@@ -1096,7 +1249,7 @@ int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, cons
     sched_step_desc(desc, sched, t, &sd);
     float* xn = t == T - 1 ? x_final : xp[t & 1];
     float* vn = t == T - 1 ? v_final : vp[t & 1];
-    rc = step_tangent_impl(&sd, w, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), vc,
+    rc = step_tangent_impl(&sd, w, dw, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), vc,
                            xn, vn, step_ws, R.step_ws, st);
     if (rc != GNCA_OK) return rc;
     xc = xn;
@@ -1117,6 +1270,19 @@ int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, cons
     }
   }
   return GNCA_OK;
+}
+
+int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                         const gnca_tangent_args* args, const float* x, const float* v, float* x_final,
+                         float* v_final, void* ws, size_t ws_bytes) {
+  return rollout_tangent_entry(desc, w, nullptr, sched, args, x, v, x_final, v_final, ws, ws_bytes);
+}
+
+int gnca_rollout_tangent_params(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                const gnca_rollout_sched* sched, const gnca_tangent_args* args, const float* x,
+                                const float* v, float* x_final, float* v_final, void* ws, size_t ws_bytes) {
+  if (!dw) return GNCA_ERR_INVALID;
+  return rollout_tangent_entry(desc, w, dw, sched, args, x, v, x_final, v_final, ws, ws_bytes);
 }
 
 size_t gnca_tangent_qr_workspace_bytes(int32_t num_dirs, int32_t B, int64_t n) {
@@ -1142,15 +1308,20 @@ size_t gnca_rollout_tangent_block_workspace_bytes(const gnca_step_desc* desc, co
   return block_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
 }
 
-int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
-                               const gnca_tangent_block_args* args, const float* x, const float* v,
-                               float* x_final, float* v_final, void* ws, size_t ws_bytes) {
+// the body of gnca_rollout_tangent_block (dw == NULL) and of gnca_rollout_tangent_block_params (dw [K])
+static int rollout_tangent_block_entry(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                       const gnca_rollout_sched* sched, const gnca_tangent_block_args* args,
+                                       const float* x, const float* v, float* x_final, float* v_final, void* ws,
+                                       size_t ws_bytes) {
   if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
   const void* ptrs[] = {x, x_final, v_final};
   const void* ptrs2[] = {v, x_final, v_final};
   if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
   if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
   if (!sched_ok(desc, sched) || !block_records_ok(sched, args)) return GNCA_ERR_INVALID;
+  // mixing the v_j alone breaks linearity in the pairs (v_j, dtheta_j)
+  if (dw && (args->flags & GNCA_TBLOCK_ORTHO)) return GNCA_ERR_INVALID;
+  if (dw && dir_aliases(dw, args->num_dirs, x_final, v_final)) return GNCA_ERR_INVALID;
   if (args->num_records > 0 && !args->log_r) return GNCA_ERR_INVALID;
   if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
   BlockTanLayout R;
@@ -1204,8 +1375,8 @@ int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w
     const uint8_t* active = sched_step_active(desc, sched, t, masks);
     if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
     for (int j = 0; j < K; ++j)
-      if ((rc = step_tangent_dir(&sd, w, xc, fire, active, vc + (size_t)j * dstride, xn, vn + (size_t)j * dstride,
-                                 step_ws, st)) != GNCA_OK)
+      if ((rc = step_tangent_dir(&sd, w, dw ? dw + j : nullptr, xc, fire, active, vc + (size_t)j * dstride, xn,
+                                 vn + (size_t)j * dstride, step_ws, st)) != GNCA_OK)
         return rc;
     xc = xn;
     vc = vn;
@@ -1227,6 +1398,20 @@ int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w
     }
   }
   return GNCA_OK;
+}
+
+int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                               const gnca_tangent_block_args* args, const float* x, const float* v,
+                               float* x_final, float* v_final, void* ws, size_t ws_bytes) {
+  return rollout_tangent_block_entry(desc, w, nullptr, sched, args, x, v, x_final, v_final, ws, ws_bytes);
+}
+
+int gnca_rollout_tangent_block_params(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                      const gnca_rollout_sched* sched, const gnca_tangent_block_args* args,
+                                      const float* x, const float* v, float* x_final, float* v_final, void* ws,
+                                      size_t ws_bytes) {
+  if (!dw) return GNCA_ERR_INVALID;
+  return rollout_tangent_block_entry(desc, w, dw, sched, args, x, v, x_final, v_final, ws, ws_bytes);
 }
 
 }  // extern "C"

@@ -675,10 +675,60 @@ def _tangent_flags(model: nn.Module, graph, hidden_only: bool):
     return flags, eps, k
 
 
+# graph parameters whose direction is accepted and ignored: in torus mode (the only mode the tangent serves) the
+# offset weights are the constant 1/k, so the query, key and scaling directions have exactly zero effect, as the
+# backward's exactly-zero gradients there; gate_mlp is never used by the step
+_IGNORED_DIRECTIONS = ("graph.query_proj.", "graph.key_proj.", "graph.scaling", "graph.gate_mlp.")
+
+
+def param_direction(model: nn.Module, fill: float = 0.0) -> dict:
+    """A correctly shaped ``dparams`` dict: one tensor per parameter a direction may perturb, filled with
+    ``fill``, on the parameter's device."""
+    return {n: torch.full_like(p.detach(), float(fill)) for n, p in model.named_parameters()
+            if n in S.DIRECTION_FIELDS}
+
+
+def _check_dparams(model: nn.Module, dparams) -> dict:
+    """ValueError unless ``dparams`` is a dict of directions for the model's parameters (pure Python, nothing is
+    drawn); returns {gnca_weights field: tensor} of the entries the kernels read."""
+    if not isinstance(dparams, dict):
+        raise ValueError(f"dparams must be a dict keyed by named_parameters() names, got {type(dparams).__name__}")
+    params = dict(model.named_parameters())
+    out = {}
+    for name, t in dparams.items():
+        if name == "perception.conv.weight":
+            raise ValueError("perception.conv.weight is frozen: the tangent carries no direction for it")
+        if name not in params:
+            if isinstance(name, str) and name.startswith("norm."):
+                raise ValueError(f"{name}: the model has no GroupNorm")
+            raise ValueError(f"unknown parameter {name!r}")
+        p = params[name]
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(p.shape):
+            raise ValueError(f"the direction of {name} has shape {tuple(getattr(t, 'shape', ()))}, the parameter "
+                             f"{tuple(p.shape)}")
+        if t.dtype != p.dtype:
+            raise ValueError(f"the direction of {name} is {t.dtype}, the parameter {p.dtype}")
+        if t.device != p.device:
+            raise ValueError(f"the direction of {name} is on {t.device}, the parameter on {p.device}")
+        if name in S.DIRECTION_FIELDS:
+            out[S.DIRECTION_FIELDS[name]] = t
+        elif not name.startswith(_IGNORED_DIRECTIONS):
+            raise ValueError(f"unknown parameter {name!r}")
+    return out
+
+
+def _direction_weights(fields: dict):
+    """(Weights struct, tensors to keep alive) of a checked direction; a missing tensor is a zero direction."""
+    return S.make_weights({k: t.detach() for k, t in fields.items()})
+
+
 def run_tangent_step(model: nn.Module, x, v, fire_rate, graph, message_gain, hidden_only: bool, *, active=None,
-                     offsets=None, fire=None):
+                     offsets=None, fire=None, dparams=None):
     """The shared body of ``NeuralCA.tangent_step`` / ``NeuralCAGraph.tangent_step``."""
-    _check_tangent_pair(model, x, v)
+    if v is None and dparams is None:
+        raise ValueError("v=None (a zero tangent) is allowed only together with dparams")
+    _check_tangent_pair(model, x, x if v is None else v)
+    dfields = None if dparams is None else _check_dparams(model, dparams)
     B, C, H, W = x.shape
     flags, eps, _ = _tangent_flags(model, graph, hidden_only)
     if isinstance(fire_rate, bool) or not isinstance(fire_rate, (int, float)):
@@ -712,7 +762,7 @@ def run_tangent_step(model: nn.Module, x, v, fire_rate, graph, message_gain, hid
         raise ValueError("active must be a [B] bool/uint8 tensor on the state's device")
     with torch.no_grad():
         x = S.check_state(x.detach(), model.n_channels)
-        v = S._dev_f32(v.detach(), "tangent")
+        v = torch.zeros_like(x) if v is None else S._dev_f32(v.detach(), "tangent")
         # the draws of forward(): one random.sample, then (rate below 1) one torch.rand on x.device
         chosen = None
         if graph is not None:
@@ -730,27 +780,38 @@ def run_tangent_step(model: nn.Module, x, v, fire_rate, graph, message_gain, hid
                float(eps))
         desc = _step_desc(key, chosen, message_gain, fire_rate, fire_mode)
         w, keep = S.make_weights(tensors)
-        out = S.step_tangent(desc, w, x, v, fire=fire, active=active)
+        if dfields is None:
+            out = S.step_tangent(desc, w, x, v, fire=fire, active=active)
+        else:
+            dw, dkeep = _direction_weights(dfields)
+            out = S.step_tangent(desc, w, x, v, fire=fire, active=active, dweights=dw)
+            del dkeep
         del keep
     return out
 
 
 def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool, *, every=None, record=None,
                         renormalize=False, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0, fire=None,
-                        seed=None, sample_base=0, offsets=None) -> TangentResult:
+                        seed=None, sample_base=0, offsets=None, dparams=None) -> TangentResult:
     """The shared body of ``NeuralCA.rollout_tangent`` / ``NeuralCAGraph.rollout_tangent``."""
-    _check_tangent_pair(model, x, v)
+    if v is None and dparams is None:
+        raise ValueError("v=None (a zero tangent) is allowed only together with dparams")
+    _check_tangent_pair(model, x, x if v is None else v)
+    dfields = None if dparams is None else _check_dparams(model, dparams)
     B, C, H, W = x.shape
     _tangent_flags(model, graph, hidden_only)
     if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
         raise ValueError(f"steps must be a non-negative int, got {steps!r}")
     if not isinstance(renormalize, bool):
         raise ValueError(f"renormalize must be a bool, got {renormalize!r}")
+    if renormalize and dfields is not None:
+        raise ValueError("renormalize=True with a parameter direction: rescaling v alone breaks linearity in the "
+                         "pair (v, dparams)")
     # the taps follow trace()'s rules; neither every nor record: nothing is recorded
     rec = [] if every is None and record is None else S.expand_record(steps, 1 if every is None else every, record)
     with torch.no_grad():
         x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
-        v = S._dev_f32(v.detach(), "tangent")
+        v = torch.zeros_like(x) if v is None else S._dev_f32(v.detach(), "tangent")
         if graph is not None and offsets is None:
             # every other schedule argument is validated before the offsets are drawn (and before a seed is)
             S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
@@ -762,8 +823,10 @@ def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool,
                                  sample_base=sample_base, offsets=offsets,
                                  sample_offsets=None if graph is None else graph.sample_offsets)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-        x_final, v_final, log_norm = S.rollout_tangent(S.RolloutCall(desc, sched), w, x, v, rec, renormalize)
-        del keep
+        dw, dkeep = (None, None) if dfields is None else _direction_weights(dfields)
+        x_final, v_final, log_norm = S.rollout_tangent(S.RolloutCall(desc, sched), w, x, v, rec, renormalize,
+                                                       dweights=dw)
+        del keep, dkeep
     return TangentResult(x_final, v_final, list(rec), log_norm)
 
 
@@ -793,8 +856,26 @@ class TangentBlockResult:
 
 def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only: bool, *, every=None, record=None,
                               orthonormalize=True, fire_rate=1.0, message_gain=None, nsteps=None, min_steps=0,
-                              fire=None, seed=None, sample_base=0, offsets=None) -> TangentBlockResult:
+                              fire=None, seed=None, sample_base=0, offsets=None,
+                              dparams=None) -> TangentBlockResult:
     """The shared body of ``NeuralCA.rollout_tangent_block`` / ``NeuralCAGraph.rollout_tangent_block``."""
+    dfields = None
+    if dparams is not None:
+        if not isinstance(dparams, (list, tuple)) or not 1 <= len(dparams) <= L.TANGENT_MAX_DIRS:
+            raise ValueError(f"dparams must be a list of K dicts, 1 <= K <= {L.TANGENT_MAX_DIRS}")
+        dfields = [_check_dparams(model, d) for d in dparams]
+        if isinstance(V, torch.Tensor) and V.dim() == 5 and V.shape[0] != len(dparams):
+            raise ValueError(f"{len(dparams)} parameter directions for a block of {V.shape[0]} tangents")
+        if orthonormalize is True:
+            raise ValueError("orthonormalize=True with parameter directions: mixing the tangents alone breaks "
+                             "linearity in the pairs (V[j], dparams[j]); pass orthonormalize=False")
+    zero_block = V is None and dfields is not None
+    if V is None and dfields is None:
+        raise ValueError("V=None (zero tangents) is allowed only together with dparams")
+    if zero_block:
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise ValueError(f"state must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
+        V = x.new_zeros((len(dfields),) + tuple(x.shape))
     if not isinstance(V, torch.Tensor) or V.dim() != 5:
         raise ValueError(f"the tangent block must be [K,B,C,H,W], got {tuple(getattr(V, 'shape', ()))}")
     if not 1 <= V.shape[0] <= L.TANGENT_MAX_DIRS:
@@ -821,6 +902,11 @@ def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only:
                                  sample_base=sample_base, offsets=offsets,
                                  sample_offsets=None if graph is None else graph.sample_offsets)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-        x_final, v_final, log_r = S.rollout_tangent_block(S.RolloutCall(desc, sched), w, x, V, rec, orthonormalize)
-        del keep
+        dws, dkeep = None, None
+        if dfields is not None:
+            pairs = [_direction_weights(f) for f in dfields]
+            dws, dkeep = [p[0] for p in pairs], [p[1] for p in pairs]
+        x_final, v_final, log_r = S.rollout_tangent_block(S.RolloutCall(desc, sched), w, x, V, rec, orthonormalize,
+                                                          dweights=dws)
+        del keep, dkeep
     return TangentBlockResult(x_final, v_final, list(rec), log_r)

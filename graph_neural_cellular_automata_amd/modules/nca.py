@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
+from ._stepper import (param_direction, RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
                        run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
                        run_step, run_tangent_step, run_trace)
 from .perception import FixedSobelPerception
@@ -38,29 +38,36 @@ class NeuralCA(nn.Module):
         out, _ = run_step(self, x, fire_rate, None, None, 0.0, False, False, active=active)
         return out
 
-    def tangent_step(self, x: torch.Tensor, v: torch.Tensor, fire_rate: float = 1.0, *, active=None, fire=None):
+    def param_direction(self, fill: float = 0.0) -> dict:
+        """A correctly shaped ``dparams`` dict filled with ``fill``: see ``NeuralCAGraph.param_direction``."""
+        return param_direction(self, fill)
+
+    def tangent_step(self, x: torch.Tensor, v: torch.Tensor, fire_rate: float = 1.0, *, active=None, fire=None,
+                     dparams=None):
         """One CA step and its forward-mode tangent, ``(x_out, J(x) v)``: see
         ``NeuralCAGraph.tangent_step`` (no ``offsets`` here)."""
-        return run_tangent_step(self, x, v, fire_rate, None, 0.0, False, active=active, fire=fire)
+        return run_tangent_step(self, x, v, fire_rate, None, 0.0, False, active=active, fire=fire, dparams=dparams)
 
     def rollout_tangent(self, x: torch.Tensor, v: torch.Tensor, steps: int, *, every=None, record=None,
                         renormalize: bool = False, fire_rate=1.0, nsteps=None, min_steps: int = 0, fire=None,
-                        seed=None, sample_base: int = 0) -> TangentResult:
+                        seed=None, sample_base: int = 0, dparams=None) -> TangentResult:
         """The tangent of a whole rollout with no tape and its per-sample log-norm curve: see
         ``NeuralCAGraph.rollout_tangent`` (no ``message_gain`` / ``offsets`` here)."""
         return run_rollout_tangent(self, x, v, steps, None, False, every=every, record=record,
                                    renormalize=renormalize, fire_rate=fire_rate, nsteps=nsteps,
-                                   min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
+                                   min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
+                                   dparams=dparams)
 
     def rollout_tangent_block(self, x: torch.Tensor, V: torch.Tensor, steps: int, *, every=None, record=None,
                               orthonormalize: bool = True, fire_rate=1.0, nsteps=None, min_steps: int = 0,
-                              fire=None, seed=None, sample_base: int = 0) -> TangentBlockResult:
+                              fire=None, seed=None, sample_base: int = 0, dparams=None) -> TangentBlockResult:
         """A block of K tangents ``V`` [K,B,C,H,W] through a whole rollout, re-orthonormalised on the
         device at every recorded step: see ``NeuralCAGraph.rollout_tangent_block`` (no ``message_gain`` /
         ``offsets`` here)."""
         return run_rollout_tangent_block(self, x, V, steps, None, False, every=every, record=record,
                                          orthonormalize=orthonormalize, fire_rate=fire_rate, nsteps=nsteps,
-                                         min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
+                                         min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
+                                         dparams=dparams)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, nsteps=None, min_steps: int = 0,
                 fire=None, seed=None, sample_base: int = 0, recompute: bool = False,

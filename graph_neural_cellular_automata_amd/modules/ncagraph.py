@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
+from ._stepper import (param_direction, RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
                        run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
                        run_step, run_tangent_step, run_trace)
 from .graph_augmentation import GraphAugmentation
@@ -72,8 +72,14 @@ class NeuralCAGraph(nn.Module):
                              self.hidden_only, return_attention, active=active)
         return (out, attn) if return_attention else out
 
+    def param_direction(self, fill: float = 0.0) -> dict:
+        """A correctly shaped ``dparams`` dict for ``tangent_step`` / ``rollout_tangent`` /
+        ``rollout_tangent_block``: one tensor filled with ``fill`` per parameter a direction may perturb
+        (``update_net.*``, ``norm.*``, ``graph.msg_proj.*``), keyed by its ``named_parameters()`` name."""
+        return param_direction(self, fill)
+
     def tangent_step(self, x: torch.Tensor, v: torch.Tensor, fire_rate: float = 1.0, *, active=None, offsets=None,
-                     fire=None):
+                     fire=None, dparams=None):
         """One CA step and its forward-mode tangent (extension, not in the reference): ``(x_out, v_out)``
         with ``x_out`` bitwise ``forward``'s result and ``v_out = J(x) v``, the Jacobian-vector product of
         the step at ``x``, by one native call (``gnca_step_tangent``) that keeps no tape.
@@ -86,14 +92,23 @@ class NeuralCAGraph(nn.Module):
         a [B,1,H,W] tensor of float32 uniforms or a uint8 / bool mask; ``active``: as ``forward``'s (an
         inactive sample passes ``x`` and ``v`` through).  Always runs under ``no_grad`` and returns
         detached tensors.  Torus mode only: a model built with ``graph_zero_padded_shift=True`` raises
-        ``ValueError`` (its offset weights depend on the state)."""
+        ``ValueError`` (its offset weights depend on the state).
+
+        ``dparams``: a direction of the WEIGHTS carried beside ``v`` (``gnca_step_tangent_params``), so that
+        ``v_out = J_x v + J_theta dparams``: a dict keyed by ``named_parameters()`` names, each tensor
+        shaped like its parameter; a missing key is a zero direction, and ``v=None`` then means a zero
+        state tangent.  ``graph.query_proj.*``, ``graph.key_proj.*``, ``graph.scaling`` and
+        ``graph.gate_mlp.*`` are accepted and ignored (their effect is exactly zero in torus mode);
+        ``perception.conv.weight`` (frozen), an unknown key, ``norm.*`` on a model without GroupNorm and a
+        wrong shape, dtype or device raise ``ValueError`` before anything is drawn.  With
+        ``dparams=None`` the call is the state tangent, bit for bit."""
         return run_tangent_step(self, x, v, fire_rate, self.graph, self.message_gain, self.hidden_only,
-                                active=active, offsets=offsets, fire=fire)
+                                active=active, offsets=offsets, fire=fire, dparams=dparams)
 
     def rollout_tangent(self, x: torch.Tensor, v: torch.Tensor, steps: int, *, every=None, record=None,
                         renormalize: bool = False, fire_rate=1.0, message_gain=None, nsteps=None,
                         min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
-                        offsets=None) -> TangentResult:
+                        offsets=None, dparams=None) -> TangentResult:
         """The tangent of a whole rollout (extension, not in the reference): where the nudge ``v`` of the
         state ``x`` is after ``steps`` steps, carried forward beside the state in one native call
         (``gnca_rollout_tangent``) with no tape, O(1) memory in ``steps``.
@@ -107,17 +122,22 @@ class NeuralCAGraph(nn.Module):
         step and carries the logs, so ``log_norm`` stays the un-renormalised curve while ``v`` cannot
         overflow: ``log_norm[-1] / steps`` is a finite-time Lyapunov exponent, with no host wait.
         Always runs under ``no_grad`` and returns detached tensors.  Bad arguments raise ``ValueError``
-        before anything is drawn or launched.  Torus mode only (see ``tangent_step``)."""
+        before anything is drawn or launched.  Torus mode only (see ``tangent_step``).
+
+        ``dparams`` (see ``tangent_step``): the same weight direction at every step
+        (``gnca_rollout_tangent_params``), so that ``v_final = dx_T/dx v + dx_T/dtheta dparams``; ``v=None``
+        is then a zero state tangent.  ``renormalize=True`` with a direction is a ``ValueError``: rescaling
+        ``v`` alone breaks linearity in the pair.  ``log_norm`` is still recorded."""
         return run_rollout_tangent(self, x, v, steps, self.graph, self.hidden_only, every=every, record=record,
                                    renormalize=renormalize, fire_rate=fire_rate,
                                    message_gain=self.message_gain if message_gain is None else message_gain,
                                    nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                   sample_base=sample_base, offsets=offsets)
+                                   sample_base=sample_base, offsets=offsets, dparams=dparams)
 
     def rollout_tangent_block(self, x: torch.Tensor, V: torch.Tensor, steps: int, *, every=None, record=None,
                               orthonormalize: bool = True, fire_rate=1.0, message_gain=None, nsteps=None,
                               min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
-                              offsets=None) -> TangentBlockResult:
+                              offsets=None, dparams=None) -> TangentBlockResult:
         """``rollout_tangent`` for a block of K directions ``V`` [K,B,C,H,W], 1 <= K <= 16, beside ONE
         primal state, in one native call (``gnca_rollout_tangent_block``): per step the primal step runs
         once and the two tangent kernels once per direction.
@@ -131,12 +151,16 @@ class NeuralCAGraph(nn.Module):
         ``rollout_tangent(x, V[j])`` and ``log_r[:, :, j]`` its ``log_norm``.
         A sample that ``nsteps`` has finished keeps its block; later records re-factor an orthonormal
         block, so their contribution to ``log_r`` is 0 within rounding.  The schedule keywords, the taps
-        and the refusals are ``rollout_tangent``'s."""
+        and the refusals are ``rollout_tangent``'s.
+
+        ``dparams``: a list of K dicts (see ``tangent_step``), direction j carrying the pair
+        ``(V[j], dparams[j])`` (``gnca_rollout_tangent_block_params``); it needs ``orthonormalize=False``
+        (mixing the tangents alone breaks linearity in the pairs), and ``V=None`` is then K zero tangents."""
         return run_rollout_tangent_block(self, x, V, steps, self.graph, self.hidden_only, every=every,
                                          record=record, orthonormalize=orthonormalize, fire_rate=fire_rate,
                                          message_gain=self.message_gain if message_gain is None else message_gain,
                                          nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                         sample_base=sample_base, offsets=offsets)
+                                         sample_base=sample_base, offsets=offsets, dparams=dparams)
 
     def rollout(self, x: torch.Tensor, steps: int, *, fire_rate=1.0, message_gain=None, nsteps=None,
                 min_steps: int = 0, fire=None, seed=None, sample_base: int = 0, offsets=None,

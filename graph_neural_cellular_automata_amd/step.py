@@ -1000,9 +1000,17 @@ def check_tangent_desc(flags: int, num_offsets: int) -> None:
         raise ValueError(ZERO_PAD_TANGENT)
 
 
-def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None):
-    """One step and its Jacobian-vector product: (x_out, v_out), x_out bitwise ``step``'s."""
-    fn = _tangent_entry("gnca_step_tangent")
+# the parameters a direction may perturb (state_dict name -> gnca_weights field): GRAD_FIELDS without the query,
+# key and scaling entries, whose directions have exactly zero effect in torus mode
+DIRECTION_FIELDS = {"update_net.0.weight": "w1", "update_net.0.bias": "b1", "update_net.2.weight": "w2",
+                    "norm.weight": "gn_weight", "norm.bias": "gn_bias",
+                    "graph.msg_proj.weight": "wm", "graph.msg_proj.bias": "bm"}
+
+
+def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None, dweights=None):
+    """One step and its Jacobian-vector product: (x_out, v_out), x_out bitwise ``step``'s.  ``dweights``: a
+    ``Weights`` struct holding a parameter direction (``gnca_step_tangent_params``)."""
+    fn = _tangent_entry("gnca_step_tangent" if dweights is None else "gnca_step_tangent_params")
     lib = L.load()
     x_out, v_out = torch.empty_like(x), torch.empty_like(v)
     if ws is None:
@@ -1012,15 +1020,17 @@ def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None):
                               f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
         ws = torch.empty(n, dtype=torch.uint8, device=x.device)
     act = _active_u8(active, desc.B, x.device)
-    rc = fn(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), _ptr(fire), _ptr(act), v.data_ptr(),
+    dw = () if dweights is None else (ctypes.byref(dweights),)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), *dw, x.data_ptr(), _ptr(fire), _ptr(act), v.data_ptr(),
             x_out.data_ptr(), v_out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
-    L.check(rc, "gnca_step_tangent")
+    L.check(rc, "gnca_step_tangent" if dweights is None else "gnca_step_tangent_params")
     return x_out, v_out
 
 
-def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormalize: bool):
-    """(x_final, v_final, log_norm float64 [R,B]) of the schedule bound in ``call``."""
-    fn = _tangent_entry("gnca_rollout_tangent")
+def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormalize: bool, dweights=None):
+    """(x_final, v_final, log_norm float64 [R,B]) of the schedule bound in ``call``.  ``dweights``: a ``Weights``
+    struct holding a parameter direction (``gnca_rollout_tangent_params``)."""
+    fn = _tangent_entry("gnca_rollout_tangent" if dweights is None else "gnca_rollout_tangent_params")
     lib = L.load()
     desc, dev = call.desc, x.device
     a = L.TangentArgs()
@@ -1037,9 +1047,10 @@ def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormaliz
                           f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     x_final, v_final = torch.empty_like(x), torch.empty_like(v)
-    rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
+    dw = () if dweights is None else (ctypes.byref(dweights),)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), *dw, ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
             v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
-    L.check(rc, "gnca_rollout_tangent")
+    L.check(rc, "gnca_rollout_tangent" if dweights is None else "gnca_rollout_tangent_params")
     return x_final, v_final, log_norm
 
 
@@ -1067,9 +1078,10 @@ def tangent_qr(v, want_r: bool = True, ws=None):
     return r, log_diag, ws
 
 
-def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orthonormalize: bool):
-    """(x_final, v_final [K,B,C,H,W], log_r float64 [R,B,K]) of the schedule bound in ``call``."""
-    fn = _tangent_entry("gnca_rollout_tangent_block")
+def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orthonormalize: bool, dweights=None):
+    """(x_final, v_final [K,B,C,H,W], log_r float64 [R,B,K]) of the schedule bound in ``call``.  ``dweights``: K
+    ``Weights`` structs, direction j's parameter direction (``gnca_rollout_tangent_block_params``)."""
+    fn = _tangent_entry("gnca_rollout_tangent_block" if dweights is None else "gnca_rollout_tangent_block_params")
     lib = L.load()
     desc, dev = call.desc, x.device
     K = v.shape[0]
@@ -1088,7 +1100,12 @@ def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orth
                           f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     x_final, v_final = torch.empty_like(x), torch.empty_like(v)
-    rc = fn(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
+    dw = ()
+    if dweights is not None:
+        if len(dweights) != K:
+            raise ValueError(f"{len(dweights)} parameter directions for a block of {K} tangents")
+        dw = ((L.Weights * K)(*dweights),)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), *dw, ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
             v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
-    L.check(rc, "gnca_rollout_tangent_block")
+    L.check(rc, "gnca_rollout_tangent_block" if dweights is None else "gnca_rollout_tangent_block_params")
     return x_final, v_final, log_r

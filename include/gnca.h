@@ -1177,6 +1177,49 @@ int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w
                                const gnca_tangent_block_args* args, const float* x, const float* v,
                                float* x_final, float* v_final, void* ws, size_t ws_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Weight-direction tangents: the three tangent entry points above with a
+ * direction dtheta of the WEIGHTS carried beside the state tangent v, so that v_out / v_final is
+ * J_x v + J_theta dtheta: where a nudge of the weights is after the step / the rollout, with no tape.
+ * The conventions are the state tangent's (masks constant, perception bank frozen, torus offset
+ * weights the constant 1/k, so that the query, key and scaling directions have exactly zero effect).
+ * With y = perceive(x), h = relu(hpre), s_z = 1/k sum_o shift_o(A_send z), cnt = live senders / k:
+ *   h'  = [hpre > 0] (W1 perceive(v) + dW1 y + db1)
+ *   u'  = (W2 h' + dW2 h
+ *          + message_gain (1 - tanh^2(m)) hidden_only(Wm s_v + dWm s_x + dbm cnt)) fire A_pre
+ *   xn' = gamma rstd (u' - mean(u') - xhat mean(xhat u')) + dgamma xhat + dbeta    (at EVERY cell, dead
+ *         and unfired ones included: GroupNorm runs on the masked field; without GroupNorm xn' = u')
+ *   v'  = v + update_gain (1 - t^2) xn';   v'[:, 3] *= post_alive(x')
+ * A sample that a masked or nsteps step leaves alone passes v through and receives no parameter
+ * term; a step with message_gain == 0 or no offsets ignores dWm, dbm.  The step is dual to
+ * gnca_step_bwd_f32: for (gx, g_theta) = VJP(gy), <gy, v'> = <gx, v> + sum_theta <g_theta, dtheta>.
+ *
+ * The direction travels as a gnca_weights `dw` whose fields w1, b1, w2, gn_weight, gn_bias, wm, bm
+ * are read, each with the shape of the weight it perturbs (NULL = a zero direction for that tensor);
+ * every other field is ignored.  The block entry takes dw [K]: direction j carries the pair
+ * (v_j, dw[j]) beside the one primal.  The workspaces are the twins': gnca_step_tangent_workspace_bytes,
+ * gnca_rollout_tangent_workspace_bytes, gnca_rollout_tangent_block_workspace_bytes.  x_out / x_final
+ * stay bitwise the twins', and a zero direction gives the twins' v_out for finite inputs.
+ *
+ * Refused before any launch: everything the twins refuse (the zero-padded shift: GNCA_ERR_UNSUPPORTED);
+ * dw == NULL or a dw tensor that is one of the outputs (GNCA_ERR_INVALID); GNCA_TANGENT_RENORM and
+ * GNCA_TBLOCK_ORTHO (GNCA_ERR_INVALID): rescaling or mixing v alone breaks linearity in the pair
+ * (v, dtheta).  log_norm / log_r are still recorded.  No class of the support set is refused: where
+ * both weight images do not fit the LDS (hidden > 128) the kernel stages them 128 hidden rows at a time.
+ * -------------------------------------------------------------------------------------------*/
+int gnca_step_tangent_params(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                             const float* x, const void* fire, const uint8_t* active, const float* v, float* x_out,
+                             float* v_out, void* ws, size_t ws_bytes, void* hip_stream);
+
+int gnca_rollout_tangent_params(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                const gnca_rollout_sched* sched, const gnca_tangent_args* args, const float* x,
+                                const float* v, float* x_final, float* v_final, void* ws, size_t ws_bytes);
+
+int gnca_rollout_tangent_block_params(const gnca_step_desc* desc, const gnca_weights* w,
+                                      const gnca_weights* dw /* [K] */, const gnca_rollout_sched* sched,
+                                      const gnca_tangent_block_args* args, const float* x, const float* v,
+                                      float* x_final, float* v_final, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,8 +10,10 @@ schedule carries an all-true ``nsteps`` so that all three paths run the schedule
 pipeline.  Every timed call is bracketed by device synchronises; a repeat is the mean over a window of
 at least ``--window`` seconds per path; per batch size one JSON line with the per-repeat values, their
 median and min-max, in ms per step.  The yardstick of the tangent is the forward-plus-backward per step.
+``--dparams`` adds a fourth leg, ``tangent_dparams``: the same rollout_tangent with a dense direction of every
+weight carried beside ``v`` (gnca_rollout_tangent_params).
 
-    python tools/bench_tangent.py [--batch 128 1024] [--repeats 5] [--window 1.0]
+    python tools/bench_tangent.py [--batch 128 1024] [--repeats 5] [--window 1.0] [--dparams]
 """
 from __future__ import annotations
 
@@ -51,8 +53,18 @@ def setup(B, dev):
     return model, x, v, kw
 
 
+def direction(model, dev):
+    """A dense N(0, 0.01) direction of every weight a direction may perturb."""
+    g = torch.Generator(device=dev).manual_seed(4321)
+    return {n: 0.01 * torch.randn(t.shape, device=dev, generator=g) for n, t in model.param_direction().items()}
+
+
 def run_tangent(model, x, v, kw):
     return model.rollout_tangent(x, v, T, **kw).v_final
+
+
+def run_tangent_dparams(model, x, v, kw):
+    return model.rollout_tangent(x, v, T, dparams=model._bench_direction, **kw).v_final
 
 
 def run_nograd(model, x, v, kw):
@@ -81,6 +93,8 @@ def timed(fn, *args):
 
 def bench(B, repeats, window, dev):
     args = setup(B, dev)
+    if "tangent_dparams" in PATHS:
+        args[0]._bench_direction = direction(args[0], dev)
     for fn in PATHS.values():   # warm-up: plans, workspaces, function attributes, the allocator
         for _ in range(2):
             timed(fn, *args)
@@ -100,6 +114,9 @@ def bench(B, repeats, window, dev):
                       min=round(min(rows[p]), 4), max=round(max(rows[p]), 4))
     res["tangent_over_fwd_bwd"] = round(res["tangent"]["median"] / res["rollout_fwd_bwd"]["median"], 4)
     res["tangent_over_nograd"] = round(res["tangent"]["median"] / res["rollout_nograd"]["median"], 4)
+    if "tangent_dparams" in PATHS:
+        res["dparams_over_tangent"] = round(res["tangent_dparams"]["median"] / res["tangent"]["median"], 4)
+        res["dparams_over_fwd_bwd"] = round(res["tangent_dparams"]["median"] / res["rollout_fwd_bwd"]["median"], 4)
     print(json.dumps(res), flush=True)
 
 
@@ -108,14 +125,20 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[128, 1024])
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=1.0)
-    ap.add_argument("--only", default=None, choices=list(PATHS), help="run one path once per batch size (for a kernel trace)")
+    ap.add_argument("--only", default=None, choices=list(PATHS) + ["tangent_dparams"],
+                    help="run one path once per batch size (for a kernel trace)")
+    ap.add_argument("--dparams", action="store_true", help="add the weight-direction leg (tangent_dparams)")
     a = ap.parse_args()
+    if a.dparams or a.only == "tangent_dparams":
+        PATHS["tangent_dparams"] = run_tangent_dparams
     if not torch.cuda.is_available():
         raise SystemExit("bench_tangent needs a ROCm GPU: a timing taken elsewhere says nothing")
     dev = torch.device("cuda:0")
     for B in a.batch:
         if a.only:
             args = setup(B, dev)
+            if a.only == "tangent_dparams":
+                args[0]._bench_direction = direction(args[0], dev)
             for _ in range(3):
                 timed(PATHS[a.only], *args)
             continue
