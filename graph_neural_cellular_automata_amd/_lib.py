@@ -174,6 +174,24 @@ class OptimDesc(ctypes.Structure):
                 ("t", OptimTensor * OPTIM_MAX_TENSORS)]
 
 
+LOSS_TANGENT_DIRS = 4    # GNCA_LOSS_TANGENT_DIRS: directions one workgroup of the loss tangent kernel serves
+FGRAD_ACCUMULATE = 1 << 0
+
+
+class ForwardGradTensor(ctypes.Structure):
+    """Mirror of gnca_forward_grad_tensor (include/gnca.h): direction k of the tensor is at dir + k * dir_stride."""
+    _fields_ = [("g", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("dir_stride", ctypes.c_int64),
+                ("numel", ctypes.c_int64)]
+
+
+class ForwardGradDesc(ctypes.Structure):
+    """Mirror of gnca_forward_grad_desc (include/gnca.h): passed by value to the kernels."""
+    _fields_ = [("K", ctypes.c_int32), ("R", ctypes.c_int32), ("B", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("dlosses", ctypes.c_void_p), ("tap_weight", ctypes.c_void_p), ("scale", ctypes.c_double),
+                ("coef", ctypes.c_void_p), ("num_tensors", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("t", ForwardGradTensor * OPTIM_MAX_TENSORS)]
+
+
 class PoolCommitDesc(ctypes.Structure):
     """Mirror of gnca_pool_commit_desc (include/gnca.h)."""
     _fields_ = [("pool_slots", ctypes.c_int64), ("sample_elems", ctypes.c_int64), ("B", ctypes.c_int32),
@@ -242,7 +260,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_tangent_qr_workspace_bytes", "gnca_tangent_qr",
            "gnca_rollout_tangent_block_workspace_bytes", "gnca_rollout_tangent_block",
            "gnca_k2_variant",
-           "gnca_step_tangent_params", "gnca_rollout_tangent_params", "gnca_rollout_tangent_block_params")
+           "gnca_step_tangent_params", "gnca_rollout_tangent_params", "gnca_rollout_tangent_block_params",
+           "gnca_loss_tangent", "gnca_rollout_objective_tangent_workspace_bytes", "gnca_rollout_objective_tangent",
+           "gnca_forward_grad")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -454,6 +474,20 @@ def load(path: str = LIB_PATH):
             lib.gnca_rollout_tangent_block_params.argtypes = [ctypes.POINTER(StepDesc), wp, wp,
                                                               ctypes.POINTER(RolloutSched),
                                                               ctypes.POINTER(TangentBlockArgs), vp, vp, vp, vp, vp, sz]
+        if hasattr(lib, "gnca_rollout_objective_tangent"):   # (likewise)
+            wp, tp = ctypes.POINTER(Weights), ctypes.POINTER(RolloutTaps)
+            lib.gnca_loss_tangent.restype = ctypes.c_int
+            lib.gnca_loss_tangent.argtypes = [i32, ctypes.POINTER(MaskedLossDesc), i32, vp, i64, vp, i64, i64, vp, i64,
+                                              vp, vp, vp]
+            lib.gnca_rollout_objective_tangent_workspace_bytes.restype = sz
+            lib.gnca_rollout_objective_tangent_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc),
+                                                                           ctypes.POINTER(RolloutSched), tp, i32]
+            lib.gnca_rollout_objective_tangent.restype = ctypes.c_int
+            lib.gnca_rollout_objective_tangent.argtypes = [ctypes.POINTER(StepDesc), wp, wp,
+                                                           ctypes.POINTER(RolloutSched), tp, i32, vp, vp, vp, vp, vp,
+                                                           vp, vp, vp, sz]
+            lib.gnca_forward_grad.restype = ctypes.c_int
+            lib.gnca_forward_grad.argtypes = [ctypes.POINTER(ForwardGradDesc), vp]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -623,6 +623,74 @@ __global__ __launch_bounds__(kThreads) void gnca_tap_inject(const TapInjectArgs 
   }
 }
 
+// The forward-mode twin of gnca_tap_loss + gnca_tap_inject: the loss of one tapped
+// state and its directional derivatives along K tangents of that state.
+constexpr int kLossTanDirs = GNCA_LOSS_TANGENT_DIRS;
+
+struct TapLossTanArgs {
+  gnca_masked_loss_desc m;    // B, H, W (and the knobs of the masked kind)
+  int K;
+  const float* state;         // [B][>= 4][H][W], samples sstride floats apart
+  size_t sstride;
+  const float* tgt;
+  long tbs;
+  const float* v;             // direction k of sample b at v + k vds + b vbs, planes H*W apart
+  size_t vds, vbs;
+  float* losses;              // [B] of this tap, or null
+  double* dlosses;            // [K][B] of this tap
+  int32_t* alive_count;       // [B] or null (masked only)
+};
+
+// grid (B, ceil(K / kLossTanDirs)): one workgroup per (sample, chunk of directions).  The loss and, for the
+// masked kind, the alive count come from the per-sample bodies above (chunk 0 stores them); then every thread
+// takes the gradient's four values of each of its cells once, in registers, and multiplies them into the
+// chunk's directions: one fp64 accumulator per direction, cells in the thread's order, channels ascending,
+// then block_sum.  A direction's sum does not depend on its slot in the chunk, so not on K.
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void gnca_tap_loss_tangent(const TapLossTanArgs a) {
+  __shared__ double red[kThreads / 64];
+  const int tid = threadIdx.x, b = blockIdx.x, k0 = (int)blockIdx.y * kLossTanDirs;
+  const size_t HW = (size_t)a.m.H * a.m.W;
+  const float* p = a.state + (size_t)b * a.sstride;
+  const float* tg = a.tgt + (size_t)b * a.tbs;
+  int32_t cnt = 0;
+  if (KIND == GNCA_TAP_PREMULT) {
+    if (blockIdx.y == 0 && a.losses != nullptr) {   // (uniform over the workgroup)
+      const float l = premult_loss_sample(a.m.H, a.m.W, p, tg, red);
+      if (tid == 0) a.losses[b] = l;
+    }
+  } else {
+    const float l = masked_loss_sample(a.m, p, tg, red, &cnt);   // (every chunk needs the count)
+    if (tid == 0 && blockIdx.y == 0) {
+      if (a.losses != nullptr) a.losses[b] = l;
+      if (a.alive_count != nullptr) a.alive_count[b] = cnt;
+    }
+  }
+  const int nk = a.K - k0 < kLossTanDirs ? a.K - k0 : kLossTanDirs;
+  const float* vb = a.v + (size_t)k0 * a.vds + (size_t)b * a.vbs;
+  double acc[kLossTanDirs];
+#pragma unroll
+  for (int j = 0; j < kLossTanDirs; ++j) acc[j] = 0.0;
+  for (size_t q = tid; q < HW; q += kThreads) {
+    float g[4];
+    if (KIND == GNCA_TAP_PREMULT) premult_grad_cell(HW, p, tg, q, 1.f, g);
+    else masked_grad_cell(a.m, HW, p, tg, q, 1.f, cnt, g);
+#pragma unroll
+    for (int j = 0; j < kLossTanDirs; ++j)
+      if (j < nk) {
+        const float* vj = vb + (size_t)j * a.vds + q;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[j] += (double)g[c] * (double)vj[c * HW];   // (the product is exact)
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < kLossTanDirs; ++j)
+    if (j < nk) {   // (uniform over the workgroup)
+      const double s = block_sum(acc[j], red);
+      if (tid == 0) a.dlosses[(size_t)(k0 + j) * a.m.B + b] = s;
+    }
+}
+
 // the stability phase: per-sample fp64 sums of the close samples (the others are not read) ...
 __global__ __launch_bounds__(kThreads) void gnca_stability_partial(int H, int W, const float* pred, long pbs,
                                                                    const float* tgt, long tbs, const uint8_t* close,
@@ -1175,6 +1243,53 @@ __global__ __launch_bounds__(kThreads) void gnca_optim_update(const gnca_optim_d
   for (int64_t e = nv + tid; e < n; e += kThreads) adam_element(k, g[e], p[e], m[e], v[e]);
 }
 
+// The forward gradient.  Neither kernel lets a product join the sum that follows it
+// in an FMA: every fp64 product and sum is rounded on its own, so the result is that of the plain formula.
+// coef[k], one workgroup per k: the samples of tap r per thread (b = tid, tid + kThreads, ...), block_sum, then
+// the taps in order.
+__global__ __launch_bounds__(kThreads) void gnca_fgrad_coef(const gnca_forward_grad_desc d) {
+#pragma clang fp contract(off)
+  __shared__ double red[kThreads / 64];
+  const int k = blockIdx.x;
+  double acc = 0.0;
+  for (int r = 0; r < d.R; ++r) {
+    const double* row = d.dlosses + ((size_t)r * d.K + k) * d.B;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < d.B; b += kThreads) s += row[b];
+    s = block_sum(s, red);
+    const double w = d.tap_weight ? (double)d.tap_weight[r] : 1.0;
+    acc = acc + w * s;
+  }
+  if (threadIdx.x == 0) d.coef[k] = d.scale * acc;
+}
+
+// g of kOptChunk elements of one tensor per workgroup, one element per thread and pass (coalesced along the
+// direction rows, whose alignment is arbitrary)
+__global__ __launch_bounds__(kThreads) void gnca_fgrad_apply(const gnca_forward_grad_desc d) {
+#pragma clang fp contract(off)
+  int i = 0;
+  int64_t c = blockIdx.x;
+  for (; i < d.num_tensors; ++i) {   // (uniform over the workgroup)
+    const int64_t nc = (d.t[i].numel + kOptChunk - 1) / kOptChunk;
+    if (c < nc) break;
+    c -= nc;
+  }
+  if (i >= d.num_tensors) return;
+  const gnca_forward_grad_tensor t = d.t[i];
+  const int64_t e0 = c * kOptChunk;
+  const int64_t e1 = t.numel - e0 < kOptChunk ? t.numel : e0 + kOptChunk;
+  const bool accumulate = (d.flags & GNCA_FGRAD_ACCUMULATE) != 0;
+  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
+    double s = 0.0;
+    for (int k = 0; k < d.K; ++k) {
+      const double term = d.coef[k] * (double)t.dir[(int64_t)k * t.dir_stride + e];
+      s = s + term;
+    }
+    const float v = (float)s;
+    t.g[e] = accumulate ? t.g[e] + v : v;
+  }
+}
+
 // does loss `o` of sample j rank before loss `mine` of sample b (torch.topk's descending order, a
 // NaN above every number; ties and NaNs among themselves by lower index)?
 __device__ __forceinline__ bool ranks_before(float o, int j, float mine, int b) {
@@ -1398,7 +1513,60 @@ int launch_tap_loss_state(const gnca_step_desc* d, const gnca_rollout_taps* taps
   return GNCA_OK;
 }
 
+// gnca_tap_loss_tangent on one state and its K tangents (m: validated by the caller; K >= 1)
+int launch_tap_loss_tangent(int kind, const gnca_masked_loss_desc* m, int K, const float* state, size_t sstride,
+                            const float* v, size_t vds, size_t vbs, const float* tgt, long tbs, float* losses,
+                            double* dlosses, int32_t* alive_count, hipStream_t st) {
+  TapLossTanArgs a;
+  a.m = *m;
+  a.K = K;
+  a.state = state; a.sstride = sstride;
+  a.tgt = tgt; a.tbs = tbs;
+  a.v = v; a.vds = vds; a.vbs = vbs;
+  a.losses = losses; a.dlosses = dlosses; a.alive_count = alive_count;
+  const dim3 grid((unsigned)m->B, (unsigned)((K + kLossTanDirs - 1) / kLossTanDirs)), block(kThreads);
+  if (kind == GNCA_TAP_MASKED) hipLaunchKernelGGL(gnca_tap_loss_tangent<GNCA_TAP_MASKED>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(gnca_tap_loss_tangent<GNCA_TAP_PREMULT>, grid, block, 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
 }  // namespace gnca
+
+extern "C" int gnca_loss_tangent(int32_t kind, const gnca_masked_loss_desc* d, int32_t num_dirs, const float* pred,
+                                 int64_t pbs, const float* v, int64_t vds, int64_t vbs, const float* target,
+                                 int64_t tbs, float* losses, double* dlosses, void* hip_stream) {
+  if (kind != GNCA_TAP_PREMULT && kind != GNCA_TAP_MASKED) return GNCA_ERR_INVALID;
+  if (!masked_desc_ok(d) || num_dirs < 1 || (num_dirs + kLossTanDirs - 1) / kLossTanDirs > 65535)
+    return GNCA_ERR_INVALID;
+  if (!pred || !v || !target || !dlosses || pbs < 0 || vds < 0 || vbs < 0 || tbs < 0) return GNCA_ERR_INVALID;
+  return launch_tap_loss_tangent(kind, d, num_dirs, pred, (size_t)pbs, v, (size_t)vds, (size_t)vbs, target, (long)tbs,
+                                 losses, dlosses, nullptr, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int gnca_forward_grad(const gnca_forward_grad_desc* d, void* hip_stream) {
+  if (!d || d->K < 1 || d->R < 1 || d->B < 1 || !d->dlosses || !d->coef) return GNCA_ERR_INVALID;
+  if (d->num_tensors < 0 || d->num_tensors > GNCA_OPTIM_MAX_TENSORS) return GNCA_ERR_INVALID;
+  if (d->flags & ~(uint32_t)GNCA_FGRAD_ACCUMULATE) return GNCA_ERR_INVALID;
+  if (((uintptr_t)d->dlosses & 7) || ((uintptr_t)d->coef & 7)) return GNCA_ERR_INVALID;
+  int64_t chunks = 0;
+  for (int i = 0; i < d->num_tensors; ++i) {
+    const gnca_forward_grad_tensor& t = d->t[i];
+    if (!t.g || !t.dir || t.numel < 0 || t.dir_stride < 0) return GNCA_ERR_INVALID;
+    chunks += (t.numel + kOptChunk - 1) / kOptChunk;
+    if (chunks > 0x7fffffffLL) return GNCA_ERR_INVALID;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  hipLaunchKernelGGL(gnca_fgrad_coef, dim3((unsigned)d->K), dim3(kThreads), 0, st, *d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && chunks > 0) {
+    hipLaunchKernelGGL(gnca_fgrad_apply, dim3((unsigned)chunks), dim3(kThreads), 0, st, *d);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
 
 extern "C" int gnca_rollout_tap_loss(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
                                      const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes,

@@ -361,6 +361,13 @@ int launch_tap_loss_state(const gnca_step_desc* d, const gnca_rollout_taps* taps
 int launch_tap_inject(const gnca_step_desc* d, const gnca_rollout_taps* taps, const float* state, const float* gl,
                       const int32_t* alive_count, const float* src, float* dst, bool full, hipStream_t st);
 
+// The loss of one tapped state and its directional derivatives along K tangents of it (gnca_tap_loss_tangent,
+// gnca_aux.hip): losses [B] or null, dlosses [K][B], alive_count [B] or null (masked kind).  Direction k of
+// sample b at v + k vds + b vbs; m: B, H, W and the masked kind's knobs, validated by the caller.
+int launch_tap_loss_tangent(int kind, const gnca_masked_loss_desc* m, int K, const float* state, size_t sstride,
+                            const float* v, size_t vds, size_t vbs, const float* tgt, long tbs, float* losses,
+                            double* dlosses, int32_t* alive_count, hipStream_t st);
+
 // hipError_t of the last failed launch on this thread (gnca_last_hip_error)
 extern thread_local int g_last_hip;
 

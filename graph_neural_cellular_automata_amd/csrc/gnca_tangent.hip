@@ -1139,6 +1139,27 @@ bool block_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, cons
   return true;
 }
 
+// gnca_rollout_objective_tangent: [masks [T][B] | step workspace | 2 x states | 2 x K tangents]
+struct ObjTanLayout {
+  size_t masks, step_ws, state, block, bytes;
+};
+
+bool obj_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps, int K,
+                    ObjTanLayout* R) {
+  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !taps_ok(d, s, taps))
+    return false;
+  if (K < 1 || K > kMaxDirs) return false;
+  size_t sw;
+  if (!tan_sched_bytes(d, s, &sw)) return false;
+  const size_t n = (size_t)d->C * d->H * d->W;
+  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
+  R->step_ws = align256(sw);
+  R->state = align256((size_t)d->B * n * sizeof(float));
+  R->block = align256((size_t)K * d->B * n * sizeof(float));
+  R->bytes = R->masks + R->step_ws + 2 * R->state + 2 * R->block;
+  return true;
+}
+
 }  // namespace
 }  // namespace gnca
 
@@ -1412,6 +1433,94 @@ int gnca_rollout_tangent_block_params(const gnca_step_desc* desc, const gnca_wei
                                       size_t ws_bytes) {
   if (!dw) return GNCA_ERR_INVALID;
   return rollout_tangent_block_entry(desc, w, dw, sched, args, x, v, x_final, v_final, ws, ws_bytes);
+}
+
+size_t gnca_rollout_objective_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                                      const gnca_rollout_taps* taps, int32_t num_dirs) {
+  ObjTanLayout R;
+  if (!desc || !sched || !taps || tangent_unsupported(desc)) return 0;
+  return obj_tan_layout(desc, sched, taps, num_dirs, &R) ? R.bytes : 0;
+}
+
+// rollout_tangent_block_entry's loop without the QR branch and the log norms; after a tapped step has written
+// (xn, vn), gnca_tap_loss_tangent reads them in place
+int gnca_rollout_objective_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                                   const gnca_rollout_sched* sched, const gnca_rollout_taps* taps, int32_t num_dirs,
+                                   const float* x, const float* v, float* x_final, float* v_final, float* losses,
+                                   double* dlosses, int32_t* alive_count, void* ws, size_t ws_bytes) {
+  if (!desc || !w || !sched || !taps || !x || !x_final || !losses || !dlosses) return GNCA_ERR_INVALID;
+  if (!v && !dw) return GNCA_ERR_INVALID;
+  if (num_dirs < 1 || num_dirs > kMaxDirs) return GNCA_ERR_INVALID;
+  {
+    const void* outs[5] = {x_final, losses, dlosses, v_final, alive_count};
+    for (int i = 0; i < 5; ++i) {
+      if (!outs[i]) continue;
+      if (outs[i] == x || outs[i] == v) return GNCA_ERR_INVALID;
+      for (int j = i + 1; j < 5; ++j)
+        if (outs[i] == outs[j]) return GNCA_ERR_INVALID;
+    }
+    if (dw && (dir_aliases(dw, num_dirs, x_final, v_final) || dir_aliases(dw, num_dirs, losses, dlosses)))
+      return GNCA_ERR_INVALID;
+  }
+  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
+  if (!sched_ok(desc, sched) || !taps_ok(desc, sched, taps)) return GNCA_ERR_INVALID;
+  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
+  ObjTanLayout R;
+  if (!obj_tan_layout(desc, sched, taps, num_dirs, &R))
+    return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(taps->stream);
+  StreamDeviceGuard dg(st);
+  const int T = sched->steps, B = desc->B, K = num_dirs;   // (T >= 1: a tap list is never empty)
+  const size_t n = (size_t)desc->C * desc->H * desc->W, dstride = (size_t)B * n;
+  char* wsb = reinterpret_cast<char*>(ws);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + R.masks;
+  float* xp[2], *vp[2];
+  for (int q = 0; q < 2; ++q) {
+    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
+    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + 2 * R.state + (size_t)q * R.block);
+  }
+  int rc;
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  const float* xc = x;
+  const float* vc = v;
+  if (!v) {   // the zero block: step 0 reads vp[1] and writes vp[0]
+    const hipError_t e = hipMemsetAsync(vp[1], 0, (size_t)K * dstride * sizeof(float), st);
+    if (e != hipSuccess) {
+      g_last_hip = (int)e;
+      return GNCA_ERR_HIP;
+    }
+    vc = vp[1];
+  }
+  int r = 0;
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* xn = t == T - 1 ? x_final : xp[t & 1];
+    float* vn = (t == T - 1 && v_final) ? v_final : vp[t & 1];
+    const void* fire = sched_step_fire(desc, sched, t);
+    const uint8_t* active = sched_step_active(desc, sched, t, masks);
+    if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
+    for (int j = 0; j < K; ++j)
+      if ((rc = step_tangent_dir(&sd, w, dw ? dw + j : nullptr, xc, fire, active, vc + (size_t)j * dstride, xn,
+                                 vn + (size_t)j * dstride, step_ws, st)) != GNCA_OK)
+        return rc;
+    xc = xn;
+    vc = vn;
+    if (r < taps->n && taps->steps[r] == t + 1) {
+      rc = launch_tap_loss_tangent(taps->kind, &taps->masked, K, xn, n, vn, dstride, n, taps->target,
+                                   (long)taps->target_bstride, losses + (size_t)r * B, dlosses + (size_t)r * K * B,
+                                   r == 0 ? alive_count : nullptr, st);
+      if (rc != GNCA_OK) return rc;
+      ++r;
+    }
+  }
+  return GNCA_OK;
 }
 
 }  // extern "C"

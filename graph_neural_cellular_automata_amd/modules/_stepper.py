@@ -910,3 +910,93 @@ def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only:
                                                           dweights=dws)
         del keep, dkeep
     return TangentBlockResult(x_final, v_final, list(rec), log_r)
+
+
+# ---------------------------------------------------------------------------------------------
+# A forward-mode objective: the tap losses and their directional derivatives along K tangents, no tape
+# ---------------------------------------------------------------------------------------------
+class ObjectiveTangent:
+    """What ``rollout_objective_tangent()`` returns: ``x_final`` [B,C,H,W], exactly the no-grad ``rollout()``'s
+    result; ``losses`` float32 [R,B], exactly ``rollout_objective()``'s; ``dlosses`` float64 [R,K,B], the
+    derivative of ``losses[r,b]`` along direction k; ``steps``, the R tapped step indices (from 1); ``v_final``
+    [K,B,C,H,W] with ``return_tangents=True``, else None.  All detached."""
+
+    __slots__ = ("x_final", "losses", "dlosses", "steps", "v_final")
+
+    def __init__(self, x_final, losses, dlosses, steps, v_final=None):
+        self.x_final, self.losses, self.dlosses, self.steps, self.v_final = x_final, losses, dlosses, steps, v_final
+
+    def __repr__(self):
+        return f"ObjectiveTangent(steps={self.steps}, dlosses={tuple(self.dlosses.shape)})"
+
+
+def run_rollout_objective_tangent(model: nn.Module, x, steps, target, graph, hidden_only: bool, *, V=None,
+                                  dparams=None, every=1, record=None, loss="premult", alpha_thr=0.2, lam_area=5e-5,
+                                  lam_bg_alpha=0.0, lam_bg_rgb=0.0, fire_rate=1.0, message_gain=None, nsteps=None,
+                                  min_steps=0, fire=None, seed=None, sample_base=0, offsets=None,
+                                  return_tangents=False) -> ObjectiveTangent:
+    """The shared body of ``NeuralCA.rollout_objective_tangent`` / ``NeuralCAGraph.rollout_objective_tangent``."""
+    from .. import loss as LS
+    # validation first (pure Python): nothing below runs, and nothing is drawn, on a bad call
+    if V is None and dparams is None:
+        raise ValueError("at least one of V (state tangents) and dparams (weight directions) must be given")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    dfields = None
+    if dparams is not None:
+        if isinstance(dparams, dict):
+            dparams = [dparams]
+        if not isinstance(dparams, (list, tuple)) or not 1 <= len(dparams) <= L.TANGENT_MAX_DIRS:
+            raise ValueError(f"dparams must be a dict or a list of K dicts, 1 <= K <= {L.TANGENT_MAX_DIRS}")
+        dfields = [_check_dparams(model, d) for d in dparams]
+    if V is not None:
+        if not isinstance(V, torch.Tensor) or V.dim() != 5:
+            raise ValueError(f"the tangent block must be [K,B,C,H,W], got {tuple(getattr(V, 'shape', ()))}")
+        if not 1 <= V.shape[0] <= L.TANGENT_MAX_DIRS:
+            raise ValueError(f"the block holds {V.shape[0]} directions; 1 <= K <= {L.TANGENT_MAX_DIRS}")
+        if dfields is not None and V.shape[0] != len(dfields):
+            raise ValueError(f"{len(dfields)} parameter directions for a block of {V.shape[0]} tangents")
+    _check_tangent_pair(model, x, x if V is None else V[0])
+    K = len(dfields) if V is None else V.shape[0]
+    B, C, H, W = x.shape
+    _tangent_flags(model, graph, hidden_only)
+    if loss not in S.TAP_KINDS:
+        raise ValueError(f"loss must be one of {sorted(S.TAP_KINDS)}, got {loss!r}")
+    _, target = LS._prepare(x[:, :4], target)
+    knobs = None
+    if loss == "masked":
+        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
+                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    rec = S.expand_record(steps, every, record)
+    if not rec:
+        raise ValueError("record is empty: a rollout objective needs at least one tapped step")
+    if not isinstance(return_tangents, bool):
+        raise ValueError(f"return_tangents must be a bool, got {return_tangents!r}")
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
+        if V is not None:
+            V = S._dev_f32(V.detach(), "tangent block")
+        if graph is not None and offsets is None:
+            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
+            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                             seed=0 if seed is None else seed, sample_base=sample_base,
+                             offsets=[[] for _ in range(steps)])
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                 sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+        tgt = target.detach().to(x.device, torch.float32)
+        tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
+        dws, dkeep = None, None
+        if dfields is not None:
+            pairs = [_direction_weights(f) for f in dfields]
+            dws, dkeep = [p[0] for p in pairs], [p[1] for p in pairs]
+        x_final, losses, dlosses, v_final = S.rollout_objective_tangent(
+            S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt), w, x, V, K, dweights=dws,
+            want_tangents=return_tangents)
+        del keep, dkeep
+    return ObjectiveTangent(x_final, losses, dlosses, list(rec), v_final)

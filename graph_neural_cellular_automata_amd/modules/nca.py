@@ -3,9 +3,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (param_direction, RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
-                       run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
-                       run_step, run_tangent_step, run_trace)
+from ._stepper import (ObjectiveTangent, param_direction, RolloutObjective, TangentBlockResult, TangentResult,
+                       TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+                       run_rollout_objective_tangent, run_rollout_tangent, run_rollout_tangent_block, run_step,
+                       run_tangent_step, run_trace)
 from .perception import FixedSobelPerception
 
 
@@ -101,6 +102,19 @@ class NeuralCA(nn.Module):
                                      lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate, nsteps=nsteps,
                                      min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
                                      recompute=recompute, checkpoint_every=checkpoint_every)
+
+    def rollout_objective_tangent(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, V=None, dparams=None,
+                                  every: int = 1, record=None, loss: str = "premult", alpha_thr: float = 0.2,
+                                  lam_area: float = 5e-5, lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0,
+                                  fire_rate=1.0, nsteps=None, min_steps: int = 0, fire=None, seed=None,
+                                  sample_base: int = 0, return_tangents: bool = False) -> ObjectiveTangent:
+        """The tap losses of ``rollout_objective`` and their derivatives along K directions, forward mode, no
+        tape: see ``NeuralCAGraph.rollout_objective_tangent`` (no ``message_gain`` / ``offsets`` here)."""
+        return run_rollout_objective_tangent(self, x, steps, target, None, False, V=V, dparams=dparams, every=every,
+                                             record=record, loss=loss, alpha_thr=alpha_thr, lam_area=lam_area,
+                                             lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate,
+                                             nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                             sample_base=sample_base, return_tangents=return_tangents)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

@@ -12,9 +12,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (param_direction, RolloutObjective, TangentBlockResult, TangentResult, TraceResult, run_rollout,
-                       run_rollout_memory, run_rollout_objective, run_rollout_tangent, run_rollout_tangent_block,
-                       run_step, run_tangent_step, run_trace)
+from ._stepper import (ObjectiveTangent, param_direction, RolloutObjective, TangentBlockResult, TangentResult,
+                       TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+                       run_rollout_objective_tangent, run_rollout_tangent, run_rollout_tangent_block, run_step,
+                       run_tangent_step, run_trace)
 from .graph_augmentation import GraphAugmentation
 from .perception import FixedSobelPerception
 
@@ -248,6 +249,39 @@ class NeuralCAGraph(nn.Module):
                                      nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                                      sample_base=sample_base, offsets=offsets, recompute=recompute,
                                      checkpoint_every=checkpoint_every)
+
+    def rollout_objective_tangent(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, V=None, dparams=None,
+                                  every: int = 1, record=None, loss: str = "premult", alpha_thr: float = 0.2,
+                                  lam_area: float = 5e-5, lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0,
+                                  fire_rate=1.0, message_gain=None, nsteps=None, min_steps: int = 0, fire=None,
+                                  seed=None, sample_base: int = 0, offsets=None,
+                                  return_tangents: bool = False) -> ObjectiveTangent:
+        """The forward-mode twin of ``rollout_objective`` (extension, not in the reference): the per-sample
+        losses of the tapped steps AND their derivatives along K directions, in one native call
+        (``gnca_rollout_objective_tangent``) with no tape, O(1) memory in ``steps`` and no backward.
+
+        ``V`` [K,B,C,H,W] are K state tangents, ``dparams`` one dict (K = 1) or a list of K dicts of weight
+        directions (see ``tangent_step``); direction k carries the pair ``(V[k], dparams[k])``, a missing
+        one is zero, and at least one of the two must be given.  Returns an ``ObjectiveTangent``:
+        ``x_final``, bitwise the no-grad ``rollout()``'s; ``losses`` float32 [R,B], bitwise
+        ``rollout_objective``'s; ``dlosses`` float64 [R,K,B], the derivative of ``losses[r,b]`` along
+        direction k, computed on the device right after the tapped step wrote its state and tangents (they
+        are never recorded); ``steps``; ``v_final`` [K,B,C,H,W] with ``return_tangents=True`` (bitwise
+        ``rollout_tangent_block(..., orthonormalize=False)``'s), else None.
+
+        The loss keywords, tap rules and target shapes are ``rollout_objective``'s; the schedule keywords
+        and the RNG consumption are ``rollout_tangent_block``'s.  Always under ``no_grad``; bad arguments
+        raise ``ValueError`` before anything is drawn or launched.  Torus mode only (see ``tangent_step``).
+        With ``forward_grad.ParamDirections`` and ``forward_grad.forward_gradient_`` this is a training step
+        without a backward: ``dlosses`` and the directions become ``.grad`` with no host wait."""
+        return run_rollout_objective_tangent(self, x, steps, target, self.graph, self.hidden_only, V=V,
+                                             dparams=dparams, every=every, record=record, loss=loss,
+                                             alpha_thr=alpha_thr, lam_area=lam_area, lam_bg_alpha=lam_bg_alpha,
+                                             lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate,
+                                             message_gain=self.message_gain if message_gain is None else message_gain,
+                                             nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                             sample_base=sample_base, offsets=offsets,
+                                             return_tangents=return_tangents)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

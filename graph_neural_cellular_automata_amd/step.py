@@ -1109,3 +1109,37 @@ def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orth
             v.data_ptr(), x_final.data_ptr(), v_final.data_ptr(), ws.data_ptr(), ws.numel())
     L.check(rc, "gnca_rollout_tangent_block" if dweights is None else "gnca_rollout_tangent_block_params")
     return x_final, v_final, log_r
+
+
+# ---------------------------------------------------------------------------------------------
+# A forward-mode objective (gnca_rollout_objective_tangent): tap losses and their directional derivatives
+# ---------------------------------------------------------------------------------------------
+def rollout_objective_tangent(call: "RolloutCall", taps: "RolloutTaps", weights, x, v, K: int, dweights=None,
+                              want_tangents: bool = False):
+    """(x_final, losses float32 [R,B], dlosses float64 [R,K,B], v_final [K,B,C,H,W] or None) of the schedule
+    bound in ``call``.  ``v``: the block [K,B,C,H,W] or None (zeros, made on the device); ``dweights``: K
+    ``Weights`` structs or None."""
+    fn = _tangent_entry("gnca_rollout_objective_tangent")
+    lib = L.load()
+    desc, dev = call.desc, x.device
+    R, B = taps.c.n, desc.B
+    if dweights is not None and len(dweights) != K:
+        raise ValueError(f"{len(dweights)} parameter directions for a block of {K} tangents")
+    taps.c.stream = stream_ptr(dev)
+    n = lib.gnca_rollout_objective_tangent_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c),
+                                                           ctypes.byref(taps.c), K)
+    if n == 0:
+        raise L.GncaError(f"unsupported objective tangent rollout: K={K} B={B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    x_final = torch.empty_like(x)
+    v_final = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=dev) if want_tangents else None
+    losses = torch.empty(R, B, dtype=torch.float32, device=dev)
+    dlosses = torch.empty(R, K, B, dtype=torch.float64, device=dev)
+    alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
+    dw = None if dweights is None else (L.Weights * K)(*dweights)
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), dw, ctypes.byref(call.c), ctypes.byref(taps.c), K,
+            x.data_ptr(), _ptr(v), x_final.data_ptr(), _ptr(v_final), losses.data_ptr(), dlosses.data_ptr(),
+            _ptr(alive), ws.data_ptr(), ws.numel())
+    L.check(rc, "gnca_rollout_objective_tangent")
+    return x_final, losses, dlosses, v_final

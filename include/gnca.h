@@ -1220,6 +1220,108 @@ int gnca_rollout_tangent_block_params(const gnca_step_desc* desc, const gnca_wei
                                       const gnca_tangent_block_args* args, const float* x, const float* v,
                                       float* x_final, float* v_final, void* ws, size_t ws_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * A forward-mode objective: the two tap losses and their directional
+ * derivatives along K tangents, computed where the tangents are, and the kernel that assembles a
+ * forward gradient from K such derivatives and K weight directions.  No new name carries the _f32
+ * suffix; the stream is named hip_stream or travels in gnca_rollout_taps.
+ *
+ * For the state S [B,C,H,W] after a tapped step and the K tangents v_k of it (channels 0..3 only):
+ *   losses[b]      bitwise gnca_loss_premult_f32 / gnca_loss_masked_f32 of S[:, :4] (the same
+ *                  per-sample body, workgroup shape and order), so bitwise the reverse-mode taps'
+ *   dlosses[k][b]  = sum over the cells q and the channels c < 4 of (double) grad_c(q) * (double) v_k[b,c,q]
+ *                  with grad the fp32 value gnca_loss_premult_bwd_f32 / gnca_loss_masked_bwd_f32 write
+ *                  for g = 1 (and the reverse-mode taps add).  Every product is exact in fp64; the sums
+ *                  are fixed-order (per thread over its cells, channels ascending, then the workgroup),
+ *                  no float atomics: bitwise reproducible, and a sample's numbers depend neither on the
+ *                  batch around it nor on K.  The masked kind counts the target's alive cells in the
+ *                  same pass.
+ * One 256-thread workgroup per (sample, GNCA_LOSS_TANGENT_DIRS directions): the state's four planes
+ * and the target are read once per workgroup and serve all its directions.
+ *
+ * gnca_loss_tangent is that kernel alone, the forward-mode counterpart of the two *_bwd_f32 entry
+ * points.  d: B, H, W of either kind and the knobs of the masked one.  pred [B,4,H,W] with its sample
+ * stride; v: direction k of sample b at v + k v_dstride + b v_bstride, four planes H*W apart;
+ * target_bstride as gnca_loss_premult_f32 (0 = one target).  losses [B] may be NULL.
+ * GNCA_ERR_INVALID before any launch: an unknown kind, a null or empty d, num_dirs < 1, a null pred,
+ * v, target or dlosses, a negative stride.
+ * -------------------------------------------------------------------------------------------*/
+#define GNCA_LOSS_TANGENT_DIRS 4   /* directions one workgroup of the loss tangent kernel serves */
+
+int gnca_loss_tangent(int32_t kind, const gnca_masked_loss_desc* d, int32_t num_dirs, const float* pred,
+                      int64_t pred_bstride, const float* v, int64_t v_dstride, int64_t v_bstride,
+                      const float* target, int64_t target_bstride, float* losses /*[B] or NULL*/,
+                      double* dlosses /*[K][B]*/, void* hip_stream);
+
+/* Bytes of device workspace the entry point below needs (0 on an invalid or unsupported desc, schedule,
+ * tap list or K).  Host-only.  [T][B] masks, one step workspace, two states, 2K tangents: apart from the
+ * masks it does not grow with T, and it does not grow with the number of taps. */
+size_t gnca_rollout_objective_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                                      const gnca_rollout_taps* taps, int32_t num_dirs);
+
+/*
+ * The block rollout without a QR and without log norms, with the kernel above run on (x', v') right
+ * after every tapped step: per step the primal runs once and the two tangent kernels once per direction.
+ *   x_final   bitwise gnca_rollout_fwd_f32's
+ *   v_final   [K][B][n] or NULL (not wanted); bitwise the block rollout's without GNCA_TBLOCK_ORTHO
+ *             (with dw: the _params twin's)
+ *   losses    f32 [R][B], bitwise gnca_rollout_fwd_taps'
+ *   dlosses   f64 [R][K][B]
+ *   v         [K][B][n], or NULL = a zero block (made on the device), which needs dw
+ *   dw        [K] weight directions, or NULL = none, which needs v
+ * Everything travels on taps->stream: no allocation, no host synchronisation, capturable.
+ * Refused before any launch: what the block rollout refuses (the zero-padded shift: GNCA_ERR_UNSUPPORTED,
+ * workspace size 0; GNCA_SCHED_RECOMPUTE / GNCA_SCHED_CHECKPOINT: GNCA_ERR_INVALID), what
+ * gnca_rollout_fwd_taps refuses about a tap list (a missing alive_count of the masked kind included),
+ * num_dirs outside 1..GNCA_TANGENT_MAX_DIRS, v and dw both NULL, a null x, x_final, losses or dlosses,
+ * and aliasing between an input (x, v, a dw tensor) and an output or between two outputs.
+ */
+int gnca_rollout_objective_tangent(const gnca_step_desc* desc, const gnca_weights* w,
+                                   const gnca_weights* dw /*[K] or NULL*/, const gnca_rollout_sched* sched,
+                                   const gnca_rollout_taps* taps, int32_t num_dirs, const float* x,
+                                   const float* v /*[K][B][n] or NULL = zeros*/, float* x_final,
+                                   float* v_final /*[K][B][n] or NULL*/, float* losses /*[R][B]*/,
+                                   double* dlosses /*[R][K][B]*/, int32_t* alive_count /*[B], masked only*/,
+                                   void* ws, size_t ws_bytes);
+
+/*
+ * The forward gradient of K directional derivatives and K directions, in two launches:
+ *   coef[k] = scale * sum_r tap_weight[r] * sum_b dlosses[r][k][b]       one workgroup per k, fp64, fixed
+ *             order (b: per thread, then the workgroup; r ascending; products and sums rounded one by one)
+ *   g[e]    = (ACCUMULATE ? g[e] : 0) + (float) sum_k coef[k] * (double) dir_k[e]
+ *             k ascending, every product and sum rounded in fp64 (never contracted), rounded to fp32 once
+ * for up to GNCA_OPTIM_MAX_TENSORS tensors; direction k of a tensor lives at dir + k * dir_stride.  A
+ * non-finite dlosses entry makes coef[k], and with it g, non-finite: reported, not hidden.  With
+ * scale = 1 / (K B) and directions drawn from N(0, I) this is the unbiased forward-gradient estimate of
+ * the batch mean of the weighted tap losses.  The descriptor travels as the kernel argument (which is why
+ * the directions are a base and a stride, not K pointers); coef is device memory, 8-B aligned, written
+ * by the first launch and read by the second.
+ * GNCA_ERR_INVALID before any launch: a null d, dlosses or coef, K, R or B < 1, num_tensors outside
+ * 0..GNCA_OPTIM_MAX_TENSORS, an unknown flag, a tensor with a null g or dir or a negative numel or stride.
+ */
+#define GNCA_FGRAD_ACCUMULATE (1u << 0)
+
+typedef struct gnca_forward_grad_tensor {
+  float* g;             /* DEVICE, contiguous fp32 [numel]: written (or accumulated into)            */
+  const float* dir;     /* direction 0 of this tensor                                                */
+  int64_t dir_stride;   /* floats between two directions of this tensor                              */
+  int64_t numel;
+} gnca_forward_grad_tensor;
+
+typedef struct gnca_forward_grad_desc {
+  int32_t K, R, B;
+  uint32_t flags;           /* GNCA_FGRAD_ACCUMULATE                                                 */
+  const double* dlosses;    /* DEVICE fp64 [R][K][B]                                                 */
+  const float* tap_weight;  /* DEVICE fp32 [R] or NULL = ones                                        */
+  double scale;
+  double* coef;             /* DEVICE fp64 [K], out                                                  */
+  int32_t num_tensors;      /* 0 .. GNCA_OPTIM_MAX_TENSORS (0: the coefficients alone)               */
+  int32_t reserved;         /* 0                                                                     */
+  gnca_forward_grad_tensor t[GNCA_OPTIM_MAX_TENSORS];
+} gnca_forward_grad_desc;
+
+int gnca_forward_grad(const gnca_forward_grad_desc* d, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
