@@ -5,13 +5,16 @@ The HIP kernels live in csrc/ and are built into libgnca.so (C ABI: include/gnca
 """
 from .damage import DamagePolicy, regrow_trace
 from .forward_grad import ParamDirections, forward_gradient_, loss_tangent
+from .gauss_newton import cg_solve
+from .loss import loss_curvature
 from .lyapunov import TangentQR, orthonormalize_tangents
 from .modules import FixedSobelPerception, GraphAugmentation, NeuralCA, NeuralCAGraph
-from .modules._stepper import ObjectiveTangent, TangentBlockResult, TangentResult
+from .modules._stepper import GaussNewtonProduct, ObjectiveTangent, TangentBlockResult, TangentResult
 from .render import CMAPS, colorize, render_rgb
 from .vitals import StateVitals, state_vitals
 
 __all__ = ["FixedSobelPerception", "NeuralCA", "GraphAugmentation", "NeuralCAGraph",
            "render_rgb", "colorize", "CMAPS", "DamagePolicy", "regrow_trace",
            "state_vitals", "StateVitals", "TangentResult", "TangentBlockResult", "TangentQR",
-           "orthonormalize_tangents", "ObjectiveTangent", "ParamDirections", "forward_gradient_", "loss_tangent"]
+           "orthonormalize_tangents", "ObjectiveTangent", "ParamDirections", "forward_gradient_", "loss_tangent",
+           "GaussNewtonProduct", "cg_solve", "loss_curvature"]

@@ -262,7 +262,9 @@ EXPORTS = ("gnca_abi_version", "gnca_status_string", "gnca_last_hip_error",
            "gnca_k2_variant",
            "gnca_step_tangent_params", "gnca_rollout_tangent_params", "gnca_rollout_tangent_block_params",
            "gnca_loss_tangent", "gnca_rollout_objective_tangent_workspace_bytes", "gnca_rollout_objective_tangent",
-           "gnca_forward_grad")
+           "gnca_forward_grad",
+           "gnca_loss_curvature", "gnca_rollout_gn_fwd_workspace_bytes", "gnca_rollout_gn_fwd",
+           "gnca_rollout_gn_bwd")
 
 PHASE_K0, PHASE_K1, PHASE_K2 = 1, 2, 4
 PHASE_ALL = 7
@@ -488,6 +490,20 @@ def load(path: str = LIB_PATH):
                                                            vp, vp, vp, sz]
             lib.gnca_forward_grad.restype = ctypes.c_int
             lib.gnca_forward_grad.argtypes = [ctypes.POINTER(ForwardGradDesc), vp]
+        if hasattr(lib, "gnca_rollout_gn_fwd"):   # (likewise)
+            wp, tp = ctypes.POINTER(Weights), ctypes.POINTER(RolloutTaps)
+            lib.gnca_loss_curvature.restype = ctypes.c_int
+            lib.gnca_loss_curvature.argtypes = [i32, ctypes.POINTER(MaskedLossDesc), vp, i64, vp, i64, vp, i64, vp, vp,
+                                                vp, vp, i64, vp]
+            lib.gnca_rollout_gn_fwd_workspace_bytes.restype = sz
+            lib.gnca_rollout_gn_fwd_workspace_bytes.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(RolloutSched),
+                                                                tp]
+            lib.gnca_rollout_gn_fwd.restype = ctypes.c_int
+            lib.gnca_rollout_gn_fwd.argtypes = [ctypes.POINTER(StepDesc), wp, wp, ctypes.POINTER(RolloutSched), tp,
+                                                vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz]
+            lib.gnca_rollout_gn_bwd.restype = ctypes.c_int
+            lib.gnca_rollout_gn_bwd.argtypes = [ctypes.POINTER(StepDesc), wp, ctypes.POINTER(RolloutSched), tp, vp, sz,
+                                                vp, ctypes.POINTER(ctypes.c_float), vp, ctypes.POINTER(Grads), vp, sz]
     if v != ABI_VERSION:
         raise GncaError(f"libgnca.so ABI version {v} != expected {ABI_VERSION}; rebuild it")
     _lib = lib

@@ -691,6 +691,138 @@ __global__ __launch_bounds__(kThreads) void gnca_tap_loss_tangent(const TapLossT
     }
 }
 
+// The Gauss-Newton twin of gnca_tap_loss_tangent: the loss of one tapped state, its
+// derivative along ONE tangent v of that state, and the loss's Gauss-Newton curvature applied to v and pulled
+// back to the state: field = P^T H P v on channels 0..3, with quad = v^T P^T H P v.
+struct TapCurvArgs {
+  gnca_masked_loss_desc m;    // B, H, W (and the knobs of the masked kind)
+  const float* state;         // [B][>= 4][H][W], samples sstride floats apart
+  size_t sstride;
+  const float* tgt;
+  long tbs;
+  const float* v;             // the tangent of sample b at v + b vbs, planes H*W apart
+  size_t vbs;
+  float* losses;              // [B] of this tap, or null
+  double* dlosses;            // [B] of this tap, or null
+  double* quad;               // [B] of this tap
+  float* field;               // sample b at field + b fbs, four planes H*W apart
+  size_t fbs;
+  int32_t* alive_count;       // [B] or null (masked only)
+};
+
+// The four field values of one cell, each an fp64 expression of the fp32 inputs, and the cell's share of the
+// quadratic form before its (2/N) factor.  No contraction: the expressions are the ones written here.
+__device__ __forceinline__ double premult_curv_cell(size_t HW, const float* p, const float* v, size_t q, double s,
+                                                    double f[4]) {
+#pragma clang fp contract(off)
+  const double a = (double)p[3 * HW + q], v3 = (double)v[3 * HW + q];
+  double fa = v3, e = v3 * v3;
+  for (int c = 0; c < 3; ++c) {
+    const double x = (double)p[c * HW + q];
+    const double pd = a * (double)v[c * HW + q] + x * v3;   // the tangent of rgb * a
+    f[c] = s * a * pd;
+    fa = fa + x * pd;
+    e = e + pd * pd;
+  }
+  f[3] = s * fa;
+  return e;
+}
+
+// grid (B): one workgroup per sample.  losses / dlosses come from the per-sample bodies and the per-cell
+// gradients the other tap kernels use (dlosses: gnca_tap_loss_tangent's sum for one direction); every field
+// value is rounded to fp32 once; quad is a fixed-order fp64 sum (per thread over its cells, then block_sum).
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void gnca_tap_curvature(const TapCurvArgs a) {
+  __shared__ double red[kThreads / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const size_t HW = (size_t)a.m.H * a.m.W;
+  const float* p = a.state + (size_t)b * a.sstride;
+  const float* tg = a.tgt + (size_t)b * a.tbs;
+  const float* vb = a.v + (size_t)b * a.vbs;
+  float* fb = a.field + (size_t)b * a.fbs;
+  int32_t cnt = 0;
+  if (KIND == GNCA_TAP_PREMULT) {
+    if (a.losses != nullptr) {   // (uniform over the workgroup)
+      const float l = premult_loss_sample(a.m.H, a.m.W, p, tg, red);
+      if (tid == 0) a.losses[b] = l;
+    }
+  } else {
+    const float l = masked_loss_sample(a.m, p, tg, red, &cnt);   // (the count is the field's denominator)
+    if (tid == 0) {
+      if (a.losses != nullptr) a.losses[b] = l;
+      if (a.alive_count != nullptr) a.alive_count[b] = cnt;
+    }
+  }
+  if (a.dlosses != nullptr) {   // (uniform over the workgroup)
+    double acc = 0.0;
+    for (size_t q = tid; q < HW; q += kThreads) {
+      float g[4];
+      if (KIND == GNCA_TAP_PREMULT) premult_grad_cell(HW, p, tg, q, 1.f, g);
+      else masked_grad_cell(a.m, HW, p, tg, q, 1.f, cnt, g);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc += (double)g[c] * (double)vb[c * HW + q];   // (the product is exact)
+    }
+    const double s = block_sum(acc, red);
+    if (tid == 0) a.dlosses[b] = s;
+  }
+  double e = 0.0;
+  if (KIND == GNCA_TAP_PREMULT) {
+    const double s = 2.0 / (4.0 * (double)HW);
+    for (size_t q = tid; q < HW; q += kThreads) {
+      double f[4];
+      e += premult_curv_cell(HW, p, vb, q, s, f);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) fb[c * HW + q] = (float)f[c];
+    }
+    e = s * block_sum(e, red);
+  } else {
+    const double D = (double)cnt + 1e-8;   // (masked_grad_cell's denominator)
+    for (size_t q = tid; q < HW; q += kThreads) {
+      const bool alive = tg[3 * HW + q] > a.m.alpha_thr;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double x = (double)vb[c * HW + q];
+        fb[c * HW + q] = alive ? (float)(2.0 * x / D) : 0.f;
+        if (alive) e += x * x;
+      }
+    }
+    e = 2.0 * block_sum(e, red) / D;
+  }
+  if (tid == 0) a.quad[b] = e;
+}
+
+// one rounded fp32 product, kept out of an FMA with the sum it feeds
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+
+struct FieldInjectArgs {
+  int B, C;
+  size_t HW;
+  const float* field;         // [B][4][H][W], contiguous
+  float scale;
+  float* dst;                 // [B,C,H,W]
+};
+
+// one thread per cell (b, q).  !FIRST: dst[b, c<4, q] += scale * field.  FIRST: every channel of dst is written,
+// scale * field on channels 0..3 and zeros on the rest (gnca_tap_inject's FULL form without a source).
+template <bool FIRST>
+__global__ __launch_bounds__(kThreads) void gnca_field_inject(const FieldInjectArgs a) {
+  const size_t HW = a.HW, total = (size_t)a.B * HW, ss = (size_t)a.C * HW;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (size_t)gridDim.x * kThreads) {
+    const size_t b = e / HW, q = e - b * HW;
+    const float* f = a.field + b * 4 * HW + q;
+    float* o = a.dst + b * ss + q;
+    if (!FIRST) {
+      for (int c = 0; c < 4; ++c) o[c * HW] = add_rn(o[c * HW], mul_rn(a.scale, f[c * HW]));
+    } else {
+      for (int c = 0; c < 4; ++c) o[c * HW] = mul_rn(a.scale, f[c * HW]);
+      for (int c = 4; c < a.C; ++c) o[c * HW] = 0.f;
+    }
+  }
+}
+
 // the stability phase: per-sample fp64 sums of the close samples (the others are not read) ...
 __global__ __launch_bounds__(kThreads) void gnca_stability_partial(int H, int W, const float* pred, long pbs,
                                                                    const float* tgt, long tbs, const uint8_t* close,
@@ -1532,7 +1664,51 @@ int launch_tap_loss_tangent(int kind, const gnca_masked_loss_desc* m, int K, con
   return GNCA_OK;
 }
 
+// gnca_tap_curvature on one state and one tangent of it (m: validated by the caller)
+int launch_tap_curvature(int kind, const gnca_masked_loss_desc* m, const float* state, size_t sstride, const float* v,
+                         size_t vbs, const float* tgt, long tbs, float* losses, double* dlosses, double* quad,
+                         float* field, size_t fbs, int32_t* alive_count, hipStream_t st) {
+  TapCurvArgs a;
+  a.m = *m;
+  a.state = state; a.sstride = sstride;
+  a.tgt = tgt; a.tbs = tbs;
+  a.v = v; a.vbs = vbs;
+  a.losses = losses; a.dlosses = dlosses; a.quad = quad;
+  a.field = field; a.fbs = fbs;
+  a.alive_count = alive_count;
+  const dim3 grid((unsigned)m->B), block(kThreads);
+  if (kind == GNCA_TAP_MASKED) hipLaunchKernelGGL(gnca_tap_curvature<GNCA_TAP_MASKED>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(gnca_tap_curvature<GNCA_TAP_PREMULT>, grid, block, 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
+int launch_field_inject(const gnca_step_desc* d, const float* field, float scale, float* dst, bool first,
+                        hipStream_t st) {
+  FieldInjectArgs a;
+  a.B = d->B; a.C = d->C;
+  a.HW = (size_t)d->H * d->W;
+  a.field = field; a.scale = scale; a.dst = dst;
+  const dim3 grid(elementwise_blocks((size_t)d->B * a.HW)), block(kThreads);
+  if (first) hipLaunchKernelGGL(gnca_field_inject<true>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(gnca_field_inject<false>, grid, block, 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { g_last_hip = (int)e; return GNCA_ERR_HIP; }
+  return GNCA_OK;
+}
+
 }  // namespace gnca
+
+extern "C" int gnca_loss_curvature(int32_t kind, const gnca_masked_loss_desc* d, const float* pred, int64_t pbs,
+                                   const float* v, int64_t vbs, const float* target, int64_t tbs, float* losses,
+                                   double* dlosses, double* quad, float* field, int64_t fbs, void* hip_stream) {
+  if (kind != GNCA_TAP_PREMULT && kind != GNCA_TAP_MASKED) return GNCA_ERR_INVALID;
+  if (!masked_desc_ok(d)) return GNCA_ERR_INVALID;
+  if (!pred || !v || !target || !quad || !field || pbs < 0 || vbs < 0 || tbs < 0 || fbs < 0) return GNCA_ERR_INVALID;
+  return launch_tap_curvature(kind, d, pred, (size_t)pbs, v, (size_t)vbs, target, (long)tbs, losses, dlosses, quad,
+                              field, (size_t)fbs, nullptr, reinterpret_cast<hipStream_t>(hip_stream));
+}
 
 extern "C" int gnca_loss_tangent(int32_t kind, const gnca_masked_loss_desc* d, int32_t num_dirs, const float* pred,
                                  int64_t pbs, const float* v, int64_t vds, int64_t vbs, const float* target,

@@ -2508,7 +2508,20 @@ struct TapsBwd {
   const float* x_final;
   const float* g_losses;
   const int32_t* alive_count;
+  // gnca_rollout_gn_bwd: tap r injects scale[r] * fields[r] (x_final, g_losses and alive_count are then unused)
+  const float* fields = nullptr;   // DEVICE [R][B][4][H][W]
+  const float* scale = nullptr;    // HOST [R]
 };
+
+// tap r of `tb` into the running cotangent: the loss gradient at `state` (gnca_tap_inject), or the precomputed
+// curvature field of that tap (gnca_field_inject; src is null there: the call has no gy)
+static int tap_inject(const gnca_step_desc* desc, const TapsBwd* tb, int r, const float* state, const float* src,
+                      float* dst, bool full, hipStream_t st) {
+  const int B = desc->B;
+  if (tb->fields)
+    return launch_field_inject(desc, tb->fields + (size_t)r * B * 4 * desc->H * desc->W, tb->scale[r], dst, full, st);
+  return launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count, src, dst, full, st);
+}
 
 // The body of gnca_rollout_bwd_f32 (tb == nullptr: exactly its launches) and of gnca_rollout_bwd_taps
 // (tb != nullptr: each tap's loss gradient joins the running cotangent between two steps; gy may
@@ -2569,8 +2582,7 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
     } else if (tl == T || !gy) {
       const float* state = tl == T ? tb->x_final : reinterpret_cast<const float*>(tp + (size_t)tl * R.T.slot);
       float* first = gb[tl & 1];
-      rc = launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count,
-                             tl == T ? gy : nullptr, first, true, st);
+      rc = tap_inject(desc, tb, r, state, tl == T ? gy : nullptr, first, true, st);
       if (rc != GNCA_OK) return rc;
       g = first;
       t_first = tl - 1;
@@ -2589,8 +2601,7 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
       if (rc != GNCA_OK) return rc;
       g = out;
       if (r >= 0 && tb->taps->steps[r] == t) {   // dL/dS_t is complete but for this tap (t >= 1: out is gb[t & 1])
-        rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out,
-                               false, st);
+        rc = tap_inject(desc, tb, r, xt, nullptr, out, false, st);
         if (rc != GNCA_OK) return rc;
         --r;
       }
@@ -2610,7 +2621,7 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
                        : static_cast<const float*>(seg_state(t - t0 - 1));
       };
       // a waiting first tap inside this segment (tl_wait = t1 + 1, not an anchor) needs S_{t1+1} too
-      const bool wait_here = tl_wait > 0 && tl_wait % k != 0;
+      const bool wait_here = tl_wait > 0 && tl_wait % k != 0 && !tb->fields;   // (a field needs no state)
       const int nfwd = t1 - t0 + (wait_here ? 1 : 0);
       if (nfwd > m1) return GNCA_ERR_INVALID;   // (cannot happen: t1 - t0 <= m1, and < m1 when waiting)
       for (int i = 0; i < nfwd; ++i) {
@@ -2626,8 +2637,7 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
         const float* state = wait_here ? static_cast<const float*>(seg_state(tl_wait - t0 - 1))
                                        : reinterpret_cast<const float*>(tp + (size_t)(tl_wait / k) * R.T.slot);
         float* first = gb[tl_wait & 1];
-        rc = launch_tap_inject(desc, tb->taps, state, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, first,
-                               true, st);
+        rc = tap_inject(desc, tb, r, state, nullptr, first, true, st);
         if (rc != GNCA_OK) return rc;
         g = first;
         --r;
@@ -2644,8 +2654,7 @@ static int rollout_bwd_impl(const gnca_step_desc* desc, const gnca_weights* w, c
         if (rc != GNCA_OK) return rc;
         g = out;
         if (r >= 0 && tb->taps->steps[r] == t) {
-          rc = launch_tap_inject(desc, tb->taps, xt, tb->g_losses + (size_t)r * B, tb->alive_count, nullptr, out,
-                                 false, st);
+          rc = tap_inject(desc, tb, r, xt, nullptr, out, false, st);
           if (rc != GNCA_OK) return rc;
           --r;
         }
@@ -2705,10 +2714,19 @@ int gnca_rollout_bwd_taps(const gnca_step_desc* desc, const gnca_weights* w, con
                           const gnca_grads* grads, void* ws, size_t ws_bytes) {
   if (!taps_ok(desc, sched, taps) || !x_final || (!gy && !g_losses) || !gx || gx == gy) return GNCA_ERR_INVALID;
   if (g_losses && taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
-  const TapsBwd tb = {taps, x_final, g_losses, alive_count};
+  const TapsBwd tb = {taps, x_final, g_losses, alive_count, nullptr, nullptr};
   // (no g_losses: the taps contribute nothing, the launches are gnca_rollout_bwd_f32's)
   return rollout_bwd_impl(desc, w, sched, tape, tape_bytes, gy, gx, grads, ws, ws_bytes, taps->stream,
                           g_losses ? &tb : nullptr);
+}
+
+int gnca_rollout_gn_bwd(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                        const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes, const float* fields,
+                        const float* scale, float* gx, const gnca_grads* grads, void* ws, size_t ws_bytes) {
+  if (!taps_ok(desc, sched, taps) || !fields || !scale || !gx || gx == fields) return GNCA_ERR_INVALID;
+  if (!(sched->flags & GNCA_SCHED_RECOMPUTE)) return GNCA_ERR_INVALID;   // gnca_rollout_gn_fwd's tape: states only
+  const TapsBwd tb = {taps, nullptr, nullptr, nullptr, fields, scale};
+  return rollout_bwd_impl(desc, w, sched, tape, tape_bytes, nullptr, gx, grads, ws, ws_bytes, taps->stream, &tb);
 }
 
 }  // extern "C"

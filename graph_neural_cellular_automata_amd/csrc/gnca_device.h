@@ -368,6 +368,19 @@ int launch_tap_loss_tangent(int kind, const gnca_masked_loss_desc* m, int K, con
                             const float* v, size_t vds, size_t vbs, const float* tgt, long tbs, float* losses,
                             double* dlosses, int32_t* alive_count, hipStream_t st);
 
+// The loss of one tapped state, its derivative along one tangent of it, and the loss's Gauss-Newton curvature
+// applied to that tangent (gnca_tap_curvature, gnca_aux.hip): losses [B] or null, dlosses [B] or null, quad [B],
+// field sample b at field + b fbs (four planes H*W apart), alive_count [B] or null (masked kind).
+int launch_tap_curvature(int kind, const gnca_masked_loss_desc* m, const float* state, size_t sstride, const float* v,
+                         size_t vbs, const float* tgt, long tbs, float* losses, double* dlosses, double* quad,
+                         float* field, size_t fbs, int32_t* alive_count, hipStream_t st);
+
+// One tap's curvature field into the backward's running cotangent (gnca_field_inject, gnca_aux.hip).
+// field [B,4,H,W] contiguous.  first == false: dst[b, c<4] += scale * field in place.  first == true: dst is
+// written whole, scale * field on channels 0..3 and zeros on the rest.
+int launch_field_inject(const gnca_step_desc* d, const float* field, float scale, float* dst, bool first,
+                        hipStream_t st);
+
 // hipError_t of the last failed launch on this thread (gnca_last_hip_error)
 extern thread_local int g_last_hip;
 

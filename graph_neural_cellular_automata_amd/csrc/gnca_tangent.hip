@@ -626,6 +626,13 @@ __global__ __launch_bounds__(kThreads) void gnca_t_zero_f64(double* p, int n) {
   if (i < n) p[i] = 0.0;
 }
 
+// zero n 16-byte vectors: a workspace block (a multiple of 256 bytes on a 256-byte boundary).  A kernel, not a
+// memset node, as gnca_rollout_bwd_taps' rows.
+__global__ __launch_bounds__(kThreads) void gnca_t_zero_v4(float4* p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads)
+    p[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 // ------------------------------------------------------------------------------------------
 // TQ: the thin QR of a tangent block v [K][B][n] (gnca_tangent_qr)
 //   TQ1 gnca_t_gram    per (sample, chunk) the fp64 Gram partials of all K (K + 1) / 2 pairs
@@ -1160,6 +1167,28 @@ bool obj_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const 
   return true;
 }
 
+// gnca_rollout_gn_fwd: [masks [T][B] | step workspace | nstate x states | 2 x tangents].  The primal's states go
+// to the tape; only a checkpointed schedule needs the two ping-pong states for the ones between two anchors.
+struct GnFwdLayout {
+  TapeLayout T;
+  size_t masks, step_ws, state, bytes;
+  int nstate;
+};
+
+bool gn_fwd_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps,
+                   GnFwdLayout* R) {
+  if (!sched_ok(d, s) || !(s->flags & GNCA_SCHED_RECOMPUTE) || !taps_ok(d, s, taps)) return false;
+  size_t sw;
+  if (!tan_sched_bytes(d, s, &sw) || !tape_layout(d, s, &R->T)) return false;
+  const size_t n = (size_t)d->C * d->H * d->W;
+  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
+  R->step_ws = align256(sw);
+  R->state = align256((size_t)d->B * n * sizeof(float));
+  R->nstate = R->T.k > 0 ? 2 : 0;
+  R->bytes = R->masks + R->step_ws + (size_t)(R->nstate + 2) * R->state;
+  return true;
+}
+
 }  // namespace
 }  // namespace gnca
 
@@ -1516,6 +1545,97 @@ int gnca_rollout_objective_tangent(const gnca_step_desc* desc, const gnca_weight
       rc = launch_tap_loss_tangent(taps->kind, &taps->masked, K, xn, n, vn, dstride, n, taps->target,
                                    (long)taps->target_bstride, losses + (size_t)r * B, dlosses + (size_t)r * K * B,
                                    r == 0 ? alive_count : nullptr, st);
+      if (rc != GNCA_OK) return rc;
+      ++r;
+    }
+  }
+  return GNCA_OK;
+}
+
+size_t gnca_rollout_gn_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                           const gnca_rollout_taps* taps) {
+  GnFwdLayout R;
+  if (!desc || !sched || !taps || tangent_unsupported(desc)) return 0;
+  return gn_fwd_layout(desc, sched, taps, &R) ? R.bytes : 0;
+}
+
+// gnca_rollout_objective_tangent's loop for one direction with the primal's states written where
+// gnca_rollout_fwd_f32 writes them on a states-only tape; after a tapped step has written (xn, vn),
+// gnca_tap_curvature reads them in place
+int gnca_rollout_gn_fwd(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
+                        const gnca_rollout_sched* sched, const gnca_rollout_taps* taps, const float* x, const float* v,
+                        float* x_final, void* tape, size_t tape_bytes, float* fields, float* losses, double* dlosses,
+                        double* quad, int32_t* alive_count, void* ws, size_t ws_bytes) {
+  if (!desc || !w || !sched || !taps || !x || !x_final || !tape || !fields || !losses || !dlosses || !quad)
+    return GNCA_ERR_INVALID;
+  if (!v && !dw) return GNCA_ERR_INVALID;
+  {
+    const void* outs[7] = {x_final, tape, fields, losses, dlosses, quad, alive_count};
+    for (int i = 0; i < 7; ++i) {
+      if (!outs[i]) continue;
+      if (outs[i] == x || outs[i] == v) return GNCA_ERR_INVALID;
+      for (int j = i + 1; j < 7; ++j)
+        if (outs[i] == outs[j]) return GNCA_ERR_INVALID;
+    }
+    if (dw && (dir_aliases(dw, 1, x_final, tape) || dir_aliases(dw, 1, fields, losses) ||
+               dir_aliases(dw, 1, dlosses, quad) || (alive_count && dir_aliases(dw, 1, alive_count, alive_count))))
+      return GNCA_ERR_INVALID;
+  }
+  if (!(sched->flags & GNCA_SCHED_RECOMPUTE)) return GNCA_ERR_INVALID;   // the tape holds states only
+  if (!sched_ok(desc, sched) || !taps_ok(desc, sched, taps)) return GNCA_ERR_INVALID;
+  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
+  GnFwdLayout R;
+  if (!gn_fwd_layout(desc, sched, taps, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (tape_bytes < R.T.bytes) return GNCA_ERR_WORKSPACE;
+  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
+  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && !sched->fire)
+    return GNCA_ERR_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(taps->stream);
+  StreamDeviceGuard dg(st);
+  const int T = sched->steps, B = desc->B, k = R.T.k;   // (T >= 1: a tap list is never empty)
+  const size_t HW = (size_t)desc->H * desc->W, n = (size_t)desc->C * HW, nbytes = (size_t)B * n * sizeof(float);
+  char* wsb = reinterpret_cast<char*>(ws);
+  char* tp = reinterpret_cast<char*>(tape);
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + R.masks;
+  float* xp[2] = {nullptr, nullptr}, *vp[2];
+  for (int q = 0; q < 2; ++q) {
+    if (R.nstate) xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
+    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)(R.nstate + q) * R.state);
+  }
+  int rc;
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  // the tape stands alone: slot 0 keeps its own copy of x, and step 0 reads it there
+  if (hipMemcpyAsync(tp, x, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
+  const float* xc = reinterpret_cast<const float*>(tp);
+  const float* vc = v;
+  if (!v) {   // the zero tangent: step 0 reads vp[1] and writes vp[0]
+    const size_t nv = R.state / sizeof(float4);
+    hipLaunchKernelGGL(gnca_t_zero_v4, dim3((unsigned)std::min<size_t>((nv + kThreads - 1) / kThreads, 4096)),
+                       dim3(kThreads), 0, st, reinterpret_cast<float4*>(vp[1]), nv);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+    vc = vp[1];
+  }
+  int r = 0;
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* xn;
+    if (t == T - 1) xn = x_final;
+    else if (k == 0) xn = reinterpret_cast<float*>(tp + (size_t)(t + 1) * R.T.slot);
+    else xn = (t + 1) % k == 0 ? reinterpret_cast<float*>(tp + (size_t)((t + 1) / k) * R.T.slot) : xp[t & 1];
+    float* vn = vp[t & 1];
+    rc = step_tangent_impl(&sd, w, dw, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks),
+                           vc, xn, vn, step_ws, R.step_ws, st);
+    if (rc != GNCA_OK) return rc;
+    xc = xn;
+    vc = vn;
+    if (r < taps->n && taps->steps[r] == t + 1) {
+      rc = launch_tap_curvature(taps->kind, &taps->masked, xn, n, vn, n, taps->target, (long)taps->target_bstride,
+                                losses + (size_t)r * B, dlosses + (size_t)r * B, quad + (size_t)r * B,
+                                fields + (size_t)r * B * 4 * HW, 4 * HW, r == 0 ? alive_count : nullptr, st);
       if (rc != GNCA_OK) return rc;
       ++r;
     }

@@ -237,3 +237,44 @@ def stability_loss(pred: torch.Tensor, target: torch.Tensor, close: torch.Tensor
     pred, target = _on_device(pred, target, "stability_loss")
     close = close.contiguous()
     return _StabilityLoss.apply(pred, target, close.view(torch.uint8) if close.dtype == torch.bool else close)
+
+
+def loss_curvature(pred: torch.Tensor, v: torch.Tensor, target: torch.Tensor, loss: str = "premult",
+                   alpha_thr: float = 0.2, lam_area: float = 5e-5, lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0):
+    """``(field, quad, losses, dlosses)`` of one tangent ``v`` [B,4,H,W] of ``pred`` [B,4,H,W]: ``field`` float32
+    [B,4,H,W], the loss's Gauss-Newton curvature applied to ``v`` and pulled back to ``pred`` (for the
+    premultiplied loss the residual term of the bilinear ``rgb * alpha`` is dropped, which keeps the curvature
+    positive semidefinite; the masked loss's penalties carry none); ``quad`` float64 [B], the quadratic form
+    ``v^T (P^T H P) v``; ``losses`` float32 [B], bitwise ``loss_premult_rgba`` / ``masked_loss``; ``dlosses``
+    float64 [B], bitwise ``loss_tangent``'s with one direction.  One launch (``gnca_loss_curvature``), no autograd.
+    ``pred`` may be the channel slice ``state[:, :4]``."""
+    from .step import TAP_KINDS
+    if loss not in TAP_KINDS:
+        raise ValueError(f"loss must be one of {sorted(TAP_KINDS)}, got {loss!r}")
+    pred, target = _prepare(pred, target)
+    B, _, H, W = pred.shape
+    if not isinstance(v, torch.Tensor) or tuple(v.shape) != (B, 4, H, W):
+        raise ValueError(f"v must be [{B},4,{H},{W}], got {tuple(getattr(v, 'shape', ()))}")
+    if v.device != pred.device or v.dtype != pred.dtype:
+        raise ValueError(f"v is {v.dtype} on {v.device}, pred {pred.dtype} on {pred.device}")
+    d = L.MaskedLossDesc()
+    d.B, d.H, d.W = B, H, W
+    if loss == "masked":
+        d.alpha_thr, d.lam_area = _number(alpha_thr, "alpha_thr"), _number(lam_area, "lam_area")
+        d.lam_bg_alpha, d.lam_bg_rgb = _number(lam_bg_alpha, "lam_bg_alpha"), _number(lam_bg_rgb, "lam_bg_rgb")
+    with torch.no_grad():
+        pred, target = _on_device(pred.detach(), target.detach(), "loss_curvature")
+        v = v.detach()
+        if not _strided_ok(v):
+            v = v.contiguous()
+        dev = pred.device
+        field = torch.empty(B, 4, H, W, dtype=torch.float32, device=dev)
+        quad = torch.empty(B, dtype=torch.float64, device=dev)
+        losses = torch.empty(B, dtype=torch.float32, device=dev)
+        dlosses = torch.empty(B, dtype=torch.float64, device=dev)
+        rc = _entry("gnca_loss_curvature")(TAP_KINDS[loss], ctypes.byref(d), pred.data_ptr(), pred.stride(0),
+                                           v.data_ptr(), v.stride(0), target.data_ptr(), _tbs(target),
+                                           losses.data_ptr(), dlosses.data_ptr(), quad.data_ptr(), field.data_ptr(),
+                                           field.stride(0), stream_ptr(dev))
+        L.check(rc, "gnca_loss_curvature")
+    return field, quad, losses, dlosses

@@ -1,6 +1,7 @@
 """Shared forward of NeuralCA / NeuralCAGraph: descriptor + weights -> one HIP step."""
 from __future__ import annotations
 
+import ctypes
 import weakref
 
 import torch
@@ -1000,3 +1001,161 @@ def run_rollout_objective_tangent(model: nn.Module, x, steps, target, graph, hid
             want_tangents=return_tangents)
         del keep, dkeep
     return ObjectiveTangent(x_final, losses, dlosses, list(rec), v_final)
+
+
+# ---------------------------------------------------------------------------------------------
+# Gauss-Newton curvature-vector products of the tap objective: one tangent forward that leaves a tape and the
+# taps' curvature fields, one BPTT that injects them
+# ---------------------------------------------------------------------------------------------
+class GaussNewtonProduct:
+    """What ``rollout_gauss_newton()`` returns: ``x_final`` [B,C,H,W], exactly the no-grad ``rollout()``'s result;
+    ``losses`` float32 [R,B], exactly ``rollout_objective()``'s; ``dlosses`` float64 [R,B], exactly
+    ``rollout_objective_tangent()``'s for this one direction; ``quad`` float64 [R,B], the loss curvature's
+    quadratic form in the tangent of each tapped state; ``steps``, the R tapped step indices (from 1);
+    ``product``, a dict keyed like ``param_direction()`` with ``G_tt dparams + G_tx v`` in the shape of each
+    parameter; ``gx`` [B,C,H,W], ``G_xt dparams + G_xx v``; ``energy``, the device float64 scalar
+    ``sum_r scale_r sum_b quad[r,b]``, which equals ``<dparams, product> + <v, gx>`` in exact arithmetic;
+    ``fields`` float32 [R,B,4,H,W] with ``return_fields=True`` (each tap's curvature field, before its scale),
+    else None.  All detached."""
+
+    __slots__ = ("x_final", "losses", "dlosses", "quad", "steps", "product", "gx", "energy", "fields")
+
+    def __init__(self, x_final, losses, dlosses, quad, steps, product, gx, energy, fields=None):
+        self.x_final, self.losses, self.dlosses, self.quad, self.steps = x_final, losses, dlosses, quad, steps
+        self.product, self.gx, self.energy, self.fields = product, gx, energy, fields
+
+    def product_flat(self) -> torch.Tensor:
+        """``product`` as one float32 vector [P] in ``forward_grad.ParamDirections`` order."""
+        return torch.cat([self.product[n].reshape(-1) for n in S.DIRECTION_FIELDS if n in self.product])
+
+    def __repr__(self):
+        return f"GaussNewtonProduct(steps={self.steps}, tensors={len(self.product)})"
+
+
+def _gauss_newton_front(model: nn.Module, x, steps, target, graph, hidden_only: bool, dparams, v, every, record, loss,
+                        alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb, tap_weights, checkpoint_every):
+    """The pure-Python validation of ``rollout_gauss_newton``: (dfields, target, knobs, rec, scale)."""
+    from .. import loss as LS
+    if v is None and dparams is None:
+        raise ValueError("at least one of v (a state tangent) and dparams (a weight direction) must be given")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    dfields = None
+    if dparams is not None:
+        if not isinstance(dparams, dict):
+            raise ValueError("dparams must be ONE dict of weight directions: a Gauss-Newton product takes one "
+                             "direction per call")
+        dfields = _check_dparams(model, dparams)
+    _check_tangent_pair(model, x, x if v is None else v)
+    B = x.shape[0]
+    _tangent_flags(model, graph, hidden_only)
+    if loss not in S.TAP_KINDS:
+        raise ValueError(f"loss must be one of {sorted(S.TAP_KINDS)}, got {loss!r}")
+    _, target = LS._prepare(x[:, :4], target)
+    knobs = None
+    if loss == "masked":
+        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
+                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    rec = S.expand_record(steps, every, record)
+    if not rec:
+        raise ValueError("record is empty: a Gauss-Newton product needs at least one tapped step")
+    S.checkpoint_interval(checkpoint_every, steps)
+    if tap_weights is None:
+        weights = [1.0] * len(rec)
+    else:
+        if isinstance(tap_weights, (torch.Tensor, str)) or not hasattr(tap_weights, "__len__"):
+            raise ValueError("tap_weights must be a sequence of R host numbers (they travel as kernel arguments)")
+        weights = [LS._number(t, "tap weight") for t in tap_weights]
+        if len(weights) != len(rec):
+            raise ValueError(f"{len(weights)} tap weights for {len(rec)} taps")
+    # scale_r as the float32 the injection kernel takes
+    scale = [ctypes.c_float(t / B).value for t in weights]
+    return dfields, target, knobs, rec, scale
+
+
+def run_rollout_gauss_newton(model: nn.Module, x, steps, target, graph, hidden_only: bool, *, dparams=None, v=None,
+                             every=1, record=None, loss="premult", alpha_thr=0.2, lam_area=5e-5, lam_bg_alpha=0.0,
+                             lam_bg_rgb=0.0, tap_weights=None, checkpoint_every=None, fire_rate=1.0,
+                             message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0,
+                             offsets=None, return_fields=False) -> GaussNewtonProduct:
+    """The shared body of ``NeuralCA.rollout_gauss_newton`` / ``NeuralCAGraph.rollout_gauss_newton``."""
+    if not isinstance(return_fields, bool):
+        raise ValueError(f"return_fields must be a bool, got {return_fields!r}")
+    # validation first (pure Python): nothing below runs, and nothing is drawn, on a bad call
+    dfields, target, knobs, rec, scale = _gauss_newton_front(
+        model, x, steps, target, graph, hidden_only, dparams, v, every, record, loss, alpha_thr, lam_area,
+        lam_bg_alpha, lam_bg_rgb, tap_weights, checkpoint_every)
+    B, C, H, W = x.shape
+    with torch.no_grad():
+        x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
+        if v is not None:
+            v = S._dev_f32(v.detach(), "tangent")
+        if graph is not None and offsets is None:
+            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
+            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                             seed=0 if seed is None else seed, sample_base=sample_base,
+                             offsets=[[] for _ in range(steps)])
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                 sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets, recompute=True,
+                                 checkpoint_every=checkpoint_every)
+        desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
+        tgt = target.detach().to(x.device, torch.float32)
+        tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
+        dw, dkeep = (None, None) if dfields is None else _direction_weights(dfields)
+        call, taps = S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt)
+        x_final, tape, fields, losses, dlosses, quad = S.rollout_gn_forward(call, taps, w, x, v, dweights=dw)
+        want = {n: p for n, p in model.named_parameters() if n in S.DIRECTION_FIELDS}
+        gx, product = S.rollout_gn_backward(call, taps, w, tape, fields, scale, x, want=want)
+        del tape, keep, dkeep
+        per_tap = quad.sum(dim=1)
+        if len(set(scale)) == 1:
+            energy = per_tap.sum() * scale[0]
+        else:
+            energy = sum(per_tap[r] * s for r, s in enumerate(scale))
+    return GaussNewtonProduct(x_final, losses, dlosses, quad, list(rec), product, gx, energy,
+                              fields if return_fields else None)
+
+
+def run_gauss_newton_memory(model: nn.Module, x_or_shape, steps: int, graph, hidden_only: bool, *, every=1,
+                            record=None, checkpoint_every=None, fire_rate=1.0, message_gain=None, nsteps=None,
+                            min_steps=0, fire=None, seed=None, sample_base=0, offsets=None) -> dict:
+    """The shared body of ``gauss_newton_memory``: bytes of the tape, the two workspaces and the fields of the
+    product ``rollout_gauss_newton()`` would run for these arguments.  Host-only; Python's and torch's RNG states
+    are put back."""
+    import random
+    if isinstance(x_or_shape, torch.Tensor):
+        shape, device = tuple(x_or_shape.shape), x_or_shape.device
+    else:
+        shape = tuple(int(t) for t in x_or_shape)
+        given = nsteps if nsteps is not None else fire
+        device = given.device if isinstance(given, torch.Tensor) else torch.device("cpu")
+    if len(shape) != 4:
+        raise ValueError(f"state must be [B,C,H,W], got {shape}")
+    if shape[1] != model.n_channels:
+        raise ValueError(f"state has {shape[1]} channels, model expects {model.n_channels}")
+    B, C, H, W = shape
+    _tangent_flags(model, graph, hidden_only)
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    rec = S.expand_record(steps, every, record)
+    if not rec:
+        raise ValueError("record is empty: a Gauss-Newton product needs at least one tapped step")
+    py_state, torch_state = random.getstate(), torch.get_rng_state()
+    try:
+        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=device, fire_rate=fire_rate,
+                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
+                                 seed=seed, sample_base=sample_base, offsets=offsets,
+                                 sample_offsets=None if graph is None else graph.sample_offsets,
+                                 recompute=True, checkpoint_every=checkpoint_every)
+    finally:
+        random.setstate(py_state)
+        torch.set_rng_state(torch_state)
+    desc, _ = _rollout_desc_host(model, shape, steps, graph, hidden_only, sched)
+    # (the sizes do not depend on the loss kind or on the target: a one-float placeholder stands for it)
+    taps = S.RolloutTaps(desc, rec, "premult", None, torch.zeros(1, 4, 1, 1))
+    return S.gn_memory(S.RolloutCall(desc, sched), taps)

@@ -3,8 +3,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (ObjectiveTangent, param_direction, RolloutObjective, TangentBlockResult, TangentResult,
-                       TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+from ._stepper import (GaussNewtonProduct, ObjectiveTangent, param_direction, RolloutObjective,
+                       TangentBlockResult, TangentResult, TraceResult, run_gauss_newton_memory, run_rollout,
+                       run_rollout_gauss_newton, run_rollout_memory, run_rollout_objective,
                        run_rollout_objective_tangent, run_rollout_tangent, run_rollout_tangent_block, run_step,
                        run_tangent_step, run_trace)
 from .perception import FixedSobelPerception
@@ -115,6 +116,30 @@ class NeuralCA(nn.Module):
                                              lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb, fire_rate=fire_rate,
                                              nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                                              sample_base=sample_base, return_tangents=return_tangents)
+
+    def rollout_gauss_newton(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, dparams=None, v=None,
+                             every: int = 1, record=None, loss: str = "premult", tap_weights=None,
+                             checkpoint_every=None, alpha_thr: float = 0.2, lam_area: float = 5e-5,
+                             lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0, fire_rate=1.0, nsteps=None,
+                             min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
+                             return_fields: bool = False) -> GaussNewtonProduct:
+        """One Gauss-Newton curvature-vector product of the tap objective, a tangent forward that leaves a tape
+        and one BPTT: see ``NeuralCAGraph.rollout_gauss_newton`` (no ``message_gain`` / ``offsets`` here)."""
+        return run_rollout_gauss_newton(self, x, steps, target, None, False, dparams=dparams, v=v, every=every,
+                                        record=record, loss=loss, alpha_thr=alpha_thr, lam_area=lam_area,
+                                        lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb, tap_weights=tap_weights,
+                                        checkpoint_every=checkpoint_every, fire_rate=fire_rate, nsteps=nsteps,
+                                        min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base,
+                                        return_fields=return_fields)
+
+    def gauss_newton_memory(self, x_or_shape, steps: int, *, every: int = 1, record=None, checkpoint_every=None,
+                            fire_rate=1.0, nsteps=None, min_steps: int = 0, fire=None, seed=None,
+                            sample_base: int = 0) -> dict:
+        """Bytes ``rollout_gauss_newton()`` with these arguments needs on the device: see
+        ``NeuralCAGraph.gauss_newton_memory``."""
+        return run_gauss_newton_memory(self, x_or_shape, steps, None, False, every=every, record=record,
+                                       checkpoint_every=checkpoint_every, fire_rate=fire_rate, nsteps=nsteps,
+                                       min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

@@ -12,8 +12,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._stepper import (ObjectiveTangent, param_direction, RolloutObjective, TangentBlockResult, TangentResult,
-                       TraceResult, run_rollout, run_rollout_memory, run_rollout_objective,
+from ._stepper import (GaussNewtonProduct, ObjectiveTangent, param_direction, RolloutObjective,
+                       TangentBlockResult, TangentResult, TraceResult, run_gauss_newton_memory, run_rollout,
+                       run_rollout_gauss_newton, run_rollout_memory, run_rollout_objective,
                        run_rollout_objective_tangent, run_rollout_tangent, run_rollout_tangent_block, run_step,
                        run_tangent_step, run_trace)
 from .graph_augmentation import GraphAugmentation
@@ -282,6 +283,56 @@ class NeuralCAGraph(nn.Module):
                                              nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
                                              sample_base=sample_base, offsets=offsets,
                                              return_tangents=return_tangents)
+
+    def rollout_gauss_newton(self, x: torch.Tensor, steps: int, target: torch.Tensor, *, dparams=None, v=None,
+                             every: int = 1, record=None, loss: str = "premult", tap_weights=None,
+                             checkpoint_every=None, alpha_thr: float = 0.2, lam_area: float = 5e-5,
+                             lam_bg_alpha: float = 0.0, lam_bg_rgb: float = 0.0, fire_rate=1.0, message_gain=None,
+                             nsteps=None, min_steps: int = 0, fire=None, seed=None, sample_base: int = 0,
+                             offsets=None,
+                             return_fields: bool = False) -> GaussNewtonProduct:
+        """One Gauss-Newton curvature-vector product of the tap objective (extension, not in the reference):
+        ``G (dparams, v) = sum_r scale_r J_r^T H_r J_r (dparams, v)`` for ``L = sum_r scale_r sum_b losses[r,b]``,
+        ``scale_r = tap_weights[r] / B`` (weights default to 1; R host numbers).  ``J_r`` is the Jacobian of the
+        state after tapped step r with respect to the weights and ``x``; ``H_r`` the loss's Gauss-Newton
+        curvature there (``loss.loss_curvature``), so ``G`` is symmetric positive semidefinite.
+
+        Two native calls: a tangent forward for the ONE direction ``(dparams, v)`` (a dict as ``tangent_step``
+        takes it, a [B,C,H,W] tangent of ``x``; a missing one is zero, at least one must be given) that writes
+        the states-only tape of ``rollout(recompute=True)`` as it goes and, after every tapped step, that
+        tap's curvature field (``gnca_rollout_gn_fwd``); then the BPTT of that tape with the scaled fields
+        injected where ``rollout_objective``'s backward injects the loss gradients
+        (``gnca_rollout_gn_bwd``).  The primal runs once; no [R,B,C,H,W] tangents are recorded.
+
+        Returns a ``GaussNewtonProduct``: ``product`` (a dict keyed like ``param_direction()``), ``gx``,
+        ``x_final`` / ``losses`` (bitwise ``rollout_objective``'s), ``dlosses`` (bitwise
+        ``rollout_objective_tangent``'s), ``quad`` and the device scalar ``energy`` =
+        ``<dparams, product> + <v, gx>`` in exact arithmetic, never negative.  ``checkpoint_every`` is
+        ``rollout()``'s and changes no number.  The loss keywords, tap rules and target shapes are
+        ``rollout_objective``'s; the schedule keywords and the RNG consumption are ``rollout_tangent``'s.
+        Always under ``no_grad``; bad arguments raise ``ValueError`` before anything is drawn or launched.
+        Torus mode only (see ``tangent_step``).  ``gauss_newton.cg_solve`` turns this into a damped
+        Gauss-Newton step."""
+        return run_rollout_gauss_newton(self, x, steps, target, self.graph, self.hidden_only, dparams=dparams, v=v,
+                                        every=every, record=record, loss=loss, alpha_thr=alpha_thr,
+                                        lam_area=lam_area, lam_bg_alpha=lam_bg_alpha, lam_bg_rgb=lam_bg_rgb,
+                                        tap_weights=tap_weights, checkpoint_every=checkpoint_every,
+                                        fire_rate=fire_rate,
+                                        message_gain=self.message_gain if message_gain is None else message_gain,
+                                        nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                        sample_base=sample_base, offsets=offsets,
+                                        return_fields=return_fields)
+
+    def gauss_newton_memory(self, x_or_shape, steps: int, *, every: int = 1, record=None, checkpoint_every=None,
+                            fire_rate=1.0, message_gain=None, nsteps=None, min_steps: int = 0, fire=None, seed=None,
+                            sample_base: int = 0, offsets=None) -> dict:
+        """Bytes ``rollout_gauss_newton()`` with these arguments needs on the device: ``tape``,
+        ``forward_workspace``, ``backward_workspace`` and ``fields``.  Host-only, as ``rollout_memory``."""
+        return run_gauss_newton_memory(self, x_or_shape, steps, self.graph, self.hidden_only, every=every,
+                                       record=record, checkpoint_every=checkpoint_every, fire_rate=fire_rate,
+                                       message_gain=self.message_gain if message_gain is None else message_gain,
+                                       nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
+                                       sample_base=sample_base, offsets=offsets)
 
     def trace(self, x: torch.Tensor, steps: int, *, every: int = 1, record=None, channels: int = 4,
               return_attention: bool = False, fire_rate=1.0, message_gain=None, seed=None,

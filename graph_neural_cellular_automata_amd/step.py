@@ -1143,3 +1143,73 @@ def rollout_objective_tangent(call: "RolloutCall", taps: "RolloutTaps", weights,
             _ptr(alive), ws.data_ptr(), ws.numel())
     L.check(rc, "gnca_rollout_objective_tangent")
     return x_final, losses, dlosses, v_final
+
+
+# ---------------------------------------------------------------------------------------------
+# Gauss-Newton products (gnca_rollout_gn_fwd / gnca_rollout_gn_bwd): the tangent forward that leaves a tape and
+# the curvature fields of the taps, and the BPTT that injects them
+# ---------------------------------------------------------------------------------------------
+def gn_memory(call: "RolloutCall", taps: "RolloutTaps") -> dict:
+    """Bytes of one Gauss-Newton product of the schedule bound in ``call``, from the host-only size queries."""
+    fn = _tangent_entry("gnca_rollout_gn_fwd_workspace_bytes")
+    lib = L.load()
+    desc = call.desc
+    n = fn(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(taps.c))
+    if n == 0:
+        raise L.GncaError(f"unsupported Gauss-Newton rollout: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode; a states-only tape)")
+    return {"tape": lib.gnca_rollout_tape_bytes(ctypes.byref(desc), ctypes.byref(call.c)),
+            "forward_workspace": n,
+            "backward_workspace": call._sizes(lib.gnca_rollout_bwd_workspace_bytes),
+            "fields": taps.c.n * desc.B * 4 * desc.H * desc.W * 4}
+
+
+def rollout_gn_forward(call: "RolloutCall", taps: "RolloutTaps", weights, x, v, dweights=None):
+    """(x_final, tape, fields float32 [R,B,4,H,W], losses float32 [R,B], dlosses float64 [R,B], quad float64 [R,B])
+    of the schedule bound in ``call`` (``recompute=True``).  ``v``: [B,C,H,W] or None (zeros, made on the device);
+    ``dweights``: a ``Weights`` struct holding the parameter direction, or None."""
+    fn = _tangent_entry("gnca_rollout_gn_fwd")
+    desc, dev = call.desc, x.device
+    R, B = taps.c.n, desc.B
+    taps.c.stream = stream_ptr(dev)
+    mem = gn_memory(call, taps)
+    ws = torch.empty(mem["forward_workspace"], dtype=torch.uint8, device=dev)
+    tape = torch.empty(max(mem["tape"], 256), dtype=torch.uint8, device=dev)
+    x_final = torch.empty_like(x)
+    fields = torch.empty(R, B, 4, desc.H, desc.W, dtype=torch.float32, device=dev)
+    losses = torch.empty(R, B, dtype=torch.float32, device=dev)
+    dlosses = torch.empty(R, B, dtype=torch.float64, device=dev)
+    quad = torch.empty(R, B, dtype=torch.float64, device=dev)
+    alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
+    rc = fn(ctypes.byref(desc), ctypes.byref(weights), None if dweights is None else ctypes.byref(dweights),
+            ctypes.byref(call.c), ctypes.byref(taps.c), x.data_ptr(), _ptr(v), x_final.data_ptr(), tape.data_ptr(),
+            tape.numel(), fields.data_ptr(), losses.data_ptr(), dlosses.data_ptr(), quad.data_ptr(), _ptr(alive),
+            ws.data_ptr(), ws.numel())
+    L.check(rc, "gnca_rollout_gn_fwd")
+    return x_final, tape, fields, losses, dlosses, quad
+
+
+def rollout_gn_backward(call: "RolloutCall", taps: "RolloutTaps", weights, tape, fields, scale: list, like,
+                        want: dict | None = None):
+    """(gx, {name: grad}) of the BPTT that injects ``scale[r] * fields[r]`` at tap r on the tape of
+    ``rollout_gn_forward``.  ``scale``: R host numbers; ``like``: a tensor of the state's shape; ``want`` as in
+    ``RolloutCall.backward``."""
+    fn = _tangent_entry("gnca_rollout_gn_bwd")
+    dev = fields.device
+    if len(scale) != taps.c.n:
+        raise ValueError(f"{len(scale)} scales for {taps.c.n} taps")
+    sc = (ctypes.c_float * len(scale))(*scale)
+    gx = torch.empty_like(like)
+    g = L.Grads()
+    grads = {}
+    for name, p in (want or {}).items():
+        t = torch.empty(p.shape, dtype=torch.float32, device=dev)
+        grads[name] = t
+        setattr(g, GRAD_FIELDS[name], t.data_ptr())
+    ws = torch.empty(call._sizes(L.load().gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=dev)
+    taps.c.stream = stream_ptr(dev)
+    rc = fn(ctypes.byref(call.desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(taps.c),
+            tape.data_ptr(), tape.numel(), fields.data_ptr(), sc, gx.data_ptr(), ctypes.byref(g), ws.data_ptr(),
+            ws.numel())
+    L.check(rc, "gnca_rollout_gn_bwd")
+    return gx, grads

@@ -1322,6 +1322,93 @@ typedef struct gnca_forward_grad_desc {
 
 int gnca_forward_grad(const gnca_forward_grad_desc* d, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gauss-Newton curvature-vector products of the tap objective:
+ *   G dtheta = sum_r scale_r J_r^T H_r J_r dtheta,   L = sum_r scale_r sum_b loss_{r,b}
+ * with J_r the Jacobian of the tapped state S_r and H_r the loss's Gauss-Newton curvature there.  Three
+ * additive entry points: the loss curvature alone, a tangent forward that leaves a tape and the fields
+ * H_r J_r (dtheta, v), and the BPTT that injects scale_r * field_r where gnca_rollout_bwd_taps injects
+ * the loss gradients.  No new name carries the _f32 suffix; the stream is named hip_stream or travels
+ * in gnca_rollout_taps.
+ *
+ * For a state S [B,>=4,H,W] (channels 0..3 are read), ONE tangent v of it and the target:
+ *   losses[b]   bitwise gnca_loss_premult_f32 / gnca_loss_masked_f32
+ *   dlosses[b]  bitwise gnca_loss_tangent's with one direction
+ *   field[b][c][q], c < 4, fp32: the curvature applied to v, pulled back to S; every value is an fp64
+ *               expression of the fp32 inputs, rounded to fp32 once
+ *   quad[b]     fp64: the quadratic form v^T (P^T H P) v, a fixed-order sum (per thread over its cells,
+ *               then the workgroup); no float atomics: bitwise reproducible, independent of the batch
+ * GNCA_TAP_PREMULT (N = 4HW, a = S_3):  pd_c = a v_c + S_c v_3 (c < 3), pd_3 = v_3,
+ *   field_c = (2/N) a pd_c (c < 3),  field_3 = (2/N) (sum_{c<3} S_c pd_c + pd_3),
+ *   quad = (2/N) sum_q sum_c pd_c^2.  The residual term (p - target) d2p/dS2 of the bilinear rgb * a is
+ *   dropped on purpose: that is what makes G positive semidefinite.
+ * GNCA_TAP_MASKED (D = n_b + 1e-8, n_b the target's alive cell count, gnca_loss_masked_bwd_f32's
+ *   denominator):  field_c = 2 alive v_c / D,  quad = 2 sum alive v_c^2 / D.  The area and background
+ *   penalties are linear or |.| and carry no curvature (|.| at 0 as its sign(0) = 0 gradient treats it);
+ *   a target with no alive cell gives an exactly zero field.
+ * In exact arithmetic sum_{c,q} field v = quad.
+ * One 256-thread workgroup per sample, cells q = tid, tid + 256, ...
+ *
+ * gnca_loss_curvature is that kernel alone.  Strides as gnca_loss_tangent: pred [B,4,H,W] with its sample
+ * stride, v and field four planes H*W apart with their sample strides, target_bstride 0 = one target.
+ * losses [B] and dlosses [B] may be NULL.  GNCA_ERR_INVALID before any launch: an unknown kind, a null or
+ * empty d, a null pred, v, target, quad or field, a negative stride.
+ * -------------------------------------------------------------------------------------------*/
+int gnca_loss_curvature(int32_t kind, const gnca_masked_loss_desc* d, const float* pred, int64_t pred_bstride,
+                        const float* v, int64_t v_bstride, const float* target, int64_t target_bstride,
+                        float* losses /*[B] or NULL*/, double* dlosses /*[B] or NULL*/, double* quad /*[B]*/,
+                        float* field /*[B][4][H][W]*/, int64_t field_bstride, void* hip_stream);
+
+/* Bytes of device workspace gnca_rollout_gn_fwd needs (0 on an invalid or unsupported desc, schedule or
+ * tap list, a schedule without GNCA_SCHED_RECOMPUTE included).  Host-only.  [T][B] masks, one step
+ * workspace, two tangents and, with GNCA_SCHED_CHECKPOINT, two states for the ones between two anchors:
+ * apart from the masks it does not grow with T, and it does not grow with the number of taps. */
+size_t gnca_rollout_gn_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
+                                           const gnca_rollout_taps* taps);
+
+/*
+ * gnca_rollout_objective_tangent's loop for one direction that also leaves the tape of the primal:
+ *   tape      byte-identical to the one gnca_rollout_fwd_f32 writes for the same inputs and schedule:
+ *             sched->flags must carry GNCA_SCHED_RECOMPUTE (states only) and may carry
+ *             GNCA_SCHED_CHECKPOINT (anchors only).  Every step writes its output state straight into its
+ *             slot; slot 0 is the copy of x; no other state copy is made.  gnca_rollout_tape_bytes,
+ *             gnca_rollout_bwd_workspace_bytes and the backward apply unchanged.
+ *   x_final   bitwise gnca_rollout_fwd_f32's
+ *   fields    f32 [R][B][4][H][W], losses f32 [R][B], dlosses f64 [R][B], quad f64 [R][B]: the kernel above
+ *             on (x', v') where they lie, one launch after every tapped step.  Nothing else grows with R.
+ *   v         [B][n], or NULL = a zero tangent (made on the device), which needs dw
+ *   dw        one weight direction, or NULL = none, which needs v
+ * Everything travels on taps->stream: no allocation, no host synchronisation, capturable.
+ * Refused before any launch: what gnca_rollout_objective_tangent refuses (the zero-padded shift:
+ * GNCA_ERR_UNSUPPORTED, workspace size 0; a bad tap list; a missing alive_count of the masked kind; v and
+ * dw both NULL), a missing GNCA_SCHED_RECOMPUTE or a null pointer (GNCA_ERR_INVALID), a short tape or
+ * workspace (GNCA_ERR_WORKSPACE), and aliasing between an input (x, v, a dw tensor) and an output or between
+ * two outputs.
+ */
+int gnca_rollout_gn_fwd(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw /*or NULL*/,
+                        const gnca_rollout_sched* sched, const gnca_rollout_taps* taps, const float* x,
+                        const float* v /*[B][n] or NULL = zeros*/, float* x_final, void* tape, size_t tape_bytes,
+                        float* fields /*[R][B][4][H][W]*/, float* losses /*[R][B]*/, double* dlosses /*[R][B]*/,
+                        double* quad /*[R][B]*/, int32_t* alive_count /*[B], masked only*/, void* ws,
+                        size_t ws_bytes);
+
+/*
+ * gnca_rollout_bwd_taps without gy whose tap r injects a precomputed field instead of a loss gradient:
+ *   g[b, c < 4, q] += (float)(scale[r] * fields[r][b][c][q])     one rounded product, one rounded add
+ * where that entry point adds the tap's gradient (the first injection writes the whole cotangent buffer:
+ * the product on channels 0..3, zeros elsewhere).  The checkpointed branch and "the steps after the last
+ * tap are not run" are kept; the step's backward and its kernels are the same.  scale: HOST f32 [R].
+ * With gnca_rollout_gn_fwd's tape and fields:
+ *   grads = G_tt dtheta + G_tx v,   gx = G_xt dtheta + G_xx v
+ * Workspace: gnca_rollout_bwd_workspace_bytes.  Everything travels on taps->stream.  GNCA_ERR_INVALID
+ * before any launch: a bad tap list, a null fields, scale or gx, a schedule without GNCA_SCHED_RECOMPUTE;
+ * a short tape or workspace: GNCA_ERR_WORKSPACE.
+ */
+int gnca_rollout_gn_bwd(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                        const gnca_rollout_taps* taps, const void* tape, size_t tape_bytes,
+                        const float* fields /*[R][B][4][H][W]*/, const float* scale /*HOST [R]*/, float* gx,
+                        const gnca_grads* grads, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
