@@ -26,6 +26,7 @@
 // stands: a lane holds hidden rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of each 32-row block, and the
 // W2 image is read in that k order.
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 
@@ -792,14 +793,14 @@ __global__ __launch_bounds__(kThreads) void gnca_t_apply(float* v, const double*
 // ------------------------------------------------------------------------------------------
 // Host
 // ------------------------------------------------------------------------------------------
-int t_check() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    g_last_hip = (int)e;
-    return GNCA_ERR_HIP;
-  }
-  return GNCA_OK;
+// a runtime call's status as a return code; a failure is kept for gnca_last_hip_error
+int t_hip(hipError_t e) {
+  if (e == hipSuccess) return GNCA_OK;
+  g_last_hip = (int)e;
+  return GNCA_ERR_HIP;
 }
+
+int t_check() { return t_hip(hipGetLastError()); }
 
 int t_device_cus() {
   static std::mutex mu;
@@ -1012,20 +1013,21 @@ int step_tangent_impl(const gnca_step_desc* desc, const gnca_weights* w, const g
   return step_tangent_dir(desc, w, dw, x, fire, active, v, x_out, v_out, ws, st);
 }
 
-// a tensor of the direction dw[0..K) that is one of the outputs
-bool dir_aliases(const gnca_weights* dw, int K, const void* o1, const void* o2) {
-  for (int j = 0; j < K; ++j) {
-    const float* t[] = {dw[j].w1, dw[j].b1, dw[j].w2, dw[j].gn_weight, dw[j].gn_bias, dw[j].wm, dw[j].bm};
-    for (const float* p : t)
-      if (p && (p == o1 || p == o2)) return true;
+// the outputs (null: not asked for) differ from one another, from the inputs x and v, and from every tensor of
+// the directions dw[0..K) (dw null: none)
+bool outputs_distinct(std::initializer_list<const void*> outs, const void* x, const void* v, const gnca_weights* dw,
+                      int K) {
+  for (auto o = outs.begin(); o != outs.end(); ++o) {
+    if (!*o) continue;
+    if (*o == x || *o == v) return false;
+    for (auto q = o + 1; q != outs.end(); ++q)
+      if (*o == *q) return false;
+    for (int j = 0; dw && j < K; ++j) {
+      const float* t[] = {dw[j].w1, dw[j].b1, dw[j].w2, dw[j].gn_weight, dw[j].gn_bias, dw[j].wm, dw[j].bm};
+      for (const float* p : t)
+        if (p == *o) return false;
+    }
   }
-  return false;
-}
-
-bool distinct(const void* const* p, int n) {
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (p[i] == p[j]) return false;
   return true;
 }
 
@@ -1042,27 +1044,53 @@ bool records_ok(const gnca_rollout_sched* s, const gnca_tangent_args* a) {
   return true;
 }
 
-// [masks [T][B] | step workspace | 2 x states | 2 x tangents | norm partials | carry | scale]
-struct RollTanLayout {
-  size_t masks, step_ws, state, off_pn, off_carry, off_scale, bytes;
-  int nchunk;
+// a well-formed schedule whose flags suit the entry: the Gauss-Newton forward writes a states-only tape
+// (RECOMPUTE, with or without CHECKPOINT), the other tangent rollouts have no tape at all
+bool tan_sched_ok(const gnca_step_desc* d, const gnca_rollout_sched* s, bool tape) {
+  if (!sched_ok(d, s)) return false;
+  return tape ? (s->flags & GNCA_SCHED_RECOMPUTE) != 0
+              : !(s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT));
+}
+
+// What every tangent rollout's workspace begins with:
+// [masks [T][B] | step workspace | nstate x states | 2 x K tangents]; an entry's own blocks follow at `bytes`.
+// nstate: the ping-pong primal states, 2, or 0 when every state goes to an un-checkpointed tape.
+struct TanRollLayout {
+  size_t masks, step_ws, state, block, bytes;
+  int nstate;
 };
 
-bool roll_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_tangent_args* a,
-                     RollTanLayout* R) {
-  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !records_ok(s, a)) return false;
+bool tan_roll_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, int K, int nstate, TanRollLayout* R) {
+  if (K < 1 || K > kMaxDirs) return false;
   size_t sw;
   if (!tan_sched_bytes(d, s, &sw)) return false;
   const size_t n = (size_t)d->C * d->H * d->W;
   R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
   R->step_ws = align256(sw);
   R->state = align256((size_t)d->B * n * sizeof(float));
-  R->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
-  size_t o = R->masks + R->step_ws + 4 * R->state;
-  R->off_pn = o;    o += align256((size_t)d->B * R->nchunk * sizeof(double));
-  R->off_carry = o; o += align256((size_t)d->B * sizeof(double));
-  R->off_scale = o; o += align256((size_t)d->B * sizeof(float));
-  R->bytes = o;
+  R->block = align256((size_t)K * d->B * n * sizeof(float));
+  R->nstate = nstate;
+  R->bytes = R->masks + R->step_ws + (size_t)nstate * R->state + 2 * R->block;
+  return true;
+}
+
+// gnca_rollout_tangent: the prefix, then [norm partials | carry | scale]
+struct RollTanLayout {
+  TanRollLayout R;
+  size_t off_pn, off_carry, off_scale, bytes;
+  int nchunk;
+};
+
+bool roll_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_tangent_args* a,
+                     RollTanLayout* L) {
+  if (!tan_sched_ok(d, s, false) || !records_ok(s, a) || !tan_roll_layout(d, s, 1, 2, &L->R)) return false;
+  const size_t n = (size_t)d->C * d->H * d->W;
+  L->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
+  size_t o = L->R.bytes;
+  L->off_pn = o;    o += align256((size_t)d->B * L->nchunk * sizeof(double));
+  L->off_carry = o; o += align256((size_t)d->B * sizeof(double));
+  L->off_scale = o; o += align256((size_t)d->B * sizeof(float));
+  L->bytes = o;
   return true;
 }
 
@@ -1116,77 +1144,135 @@ bool block_records_ok(const gnca_rollout_sched* s, const gnca_tangent_block_args
   return records_ok(s, &one);
 }
 
-// [masks [T][B] | step workspace | 2 x states | 2 x K tangents | norm partials | scale | carry [B][K] | QR workspace]
+// gnca_rollout_tangent_block: the prefix, then [norm partials | scale | carry [B][16] | QR workspace]
 struct BlockTanLayout {
-  size_t masks, step_ws, state, block, off_pn, off_scale, off_carry, off_qr, bytes;
+  TanRollLayout R;
+  size_t off_pn, off_scale, off_carry, off_qr, bytes;
   int nchunk;
   QrLayout Q;
 };
 
 bool block_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_tangent_block_args* a,
-                      BlockTanLayout* R) {
-  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !block_records_ok(s, a))
+                      BlockTanLayout* L) {
+  if (!tan_sched_ok(d, s, false) || !block_records_ok(s, a) || !tan_roll_layout(d, s, a->num_dirs, 2, &L->R))
     return false;
-  size_t sw;
-  if (!tan_sched_bytes(d, s, &sw)) return false;
-  const int K = a->num_dirs;
   const size_t n = (size_t)d->C * d->H * d->W;
-  if (!qr_layout(K, d->B, (int64_t)n, &R->Q)) return false;
-  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
-  R->step_ws = align256(sw);
-  R->state = align256((size_t)d->B * n * sizeof(float));
-  R->block = align256((size_t)K * d->B * n * sizeof(float));
-  R->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
-  size_t o = R->masks + R->step_ws + 2 * R->state + 2 * R->block;
-  R->off_pn = o;    o += align256((size_t)d->B * R->nchunk * sizeof(double));
-  R->off_scale = o; o += align256((size_t)d->B * sizeof(float));
-  R->off_carry = o; o += align256((size_t)d->B * kMaxDirs * sizeof(double));
-  R->off_qr = o;    o += R->Q.bytes;
-  R->bytes = o;
+  if (!qr_layout(a->num_dirs, d->B, (int64_t)n, &L->Q)) return false;
+  L->nchunk = (int)((n + kNormChunk - 1) / kNormChunk);
+  size_t o = L->R.bytes;
+  L->off_pn = o;    o += align256((size_t)d->B * L->nchunk * sizeof(double));
+  L->off_scale = o; o += align256((size_t)d->B * sizeof(float));
+  L->off_carry = o; o += align256((size_t)d->B * kMaxDirs * sizeof(double));
+  L->off_qr = o;    o += L->Q.bytes;
+  L->bytes = o;
   return true;
 }
 
-// gnca_rollout_objective_tangent: [masks [T][B] | step workspace | 2 x states | 2 x K tangents]
-struct ObjTanLayout {
-  size_t masks, step_ws, state, block, bytes;
-};
-
+// gnca_rollout_objective_tangent: the prefix alone
 bool obj_tan_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps, int K,
-                    ObjTanLayout* R) {
-  if (!sched_ok(d, s) || (s->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) || !taps_ok(d, s, taps))
-    return false;
-  if (K < 1 || K > kMaxDirs) return false;
-  size_t sw;
-  if (!tan_sched_bytes(d, s, &sw)) return false;
-  const size_t n = (size_t)d->C * d->H * d->W;
-  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
-  R->step_ws = align256(sw);
-  R->state = align256((size_t)d->B * n * sizeof(float));
-  R->block = align256((size_t)K * d->B * n * sizeof(float));
-  R->bytes = R->masks + R->step_ws + 2 * R->state + 2 * R->block;
-  return true;
+                    TanRollLayout* R) {
+  return tan_sched_ok(d, s, false) && taps_ok(d, s, taps) && tan_roll_layout(d, s, K, 2, R);
 }
 
-// gnca_rollout_gn_fwd: [masks [T][B] | step workspace | nstate x states | 2 x tangents].  The primal's states go
-// to the tape; only a checkpointed schedule needs the two ping-pong states for the ones between two anchors.
+// gnca_rollout_gn_fwd: the prefix for one direction, and the tape.  The primal's states go to the tape; only a
+// checkpointed schedule needs the two ping-pong states for the ones between two anchors.
 struct GnFwdLayout {
+  TanRollLayout R;
   TapeLayout T;
-  size_t masks, step_ws, state, bytes;
-  int nstate;
 };
 
 bool gn_fwd_layout(const gnca_step_desc* d, const gnca_rollout_sched* s, const gnca_rollout_taps* taps,
-                   GnFwdLayout* R) {
-  if (!sched_ok(d, s) || !(s->flags & GNCA_SCHED_RECOMPUTE) || !taps_ok(d, s, taps)) return false;
-  size_t sw;
-  if (!tan_sched_bytes(d, s, &sw) || !tape_layout(d, s, &R->T)) return false;
-  const size_t n = (size_t)d->C * d->H * d->W;
-  R->masks = align256((size_t)std::max(s->steps, 1) * d->B);
-  R->step_ws = align256(sw);
-  R->state = align256((size_t)d->B * n * sizeof(float));
-  R->nstate = R->T.k > 0 ? 2 : 0;
-  R->bytes = R->masks + R->step_ws + (size_t)(R->nstate + 2) * R->state;
-  return true;
+                   GnFwdLayout* L) {
+  return tan_sched_ok(d, s, true) && taps_ok(d, s, taps) && tape_layout(d, s, &L->T) &&
+         tan_roll_layout(d, s, 1, L->T.k > 0 ? 2 : 0, &L->R);
+}
+
+// The refusals every tangent rollout entry shares once its own arguments have passed, in the order they win.
+// tape: as tan_sched_ok; laid_out: the entry's layout exists; fits: the caller's buffers hold it.
+int tan_roll_check(const gnca_step_desc* d, const gnca_rollout_sched* s, bool tape, bool laid_out, bool fits) {
+  if (!tan_sched_ok(d, s, tape)) return GNCA_ERR_INVALID;
+  if (tangent_unsupported(d)) return GNCA_ERR_UNSUPPORTED;
+  if (!laid_out) return outside_support(d) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
+  if (!fits) return GNCA_ERR_WORKSPACE;
+  if ((d->fire_mode == GNCA_FIRE_RAND_F32 || d->fire_mode == GNCA_FIRE_MASK_U8) && s->steps > 0 && !s->fire)
+    return GNCA_ERR_INVALID;
+  return GNCA_OK;
+}
+
+// One rollout of the step and K tangents of it.
+struct TanRoll {
+  int K;
+  const gnca_weights* dw;      // [K] weight directions, or null: state tangents alone
+  const float *x, *v;          // v null: a zero block, made on the device
+  float *x_final, *v_final;    // v_final null: the last tangents stay in the workspace
+  char* tape;                  // the states-only tape (slot 0 takes a copy of x), or null: ping-pong states only
+  size_t slot;                 // ... its slot size
+  int every;                   // ... its anchor interval, 0: every state has a slot
+  double* carry;               // ncarry log-norm carries to zero before the first step, or null
+  int ncarry;
+};
+
+// After step t has written (xn, vn [K]), `after(t, xn, vn)` records what the entry records there; its return
+// code, unless GNCA_OK, ends the rollout.  Zero steps copy the inputs out.
+template <class After>
+int tangent_rollout(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
+                    const TanRollLayout& R, char* wsb, const TanRoll& a, hipStream_t st, After&& after) {
+  const int T = sched->steps, B = desc->B, K = a.K;
+  const size_t dstride = (size_t)B * desc->C * desc->H * desc->W, nbytes = dstride * sizeof(float);
+  int rc;
+  if (T == 0) {
+    if ((rc = t_hip(hipMemcpyAsync(a.x_final, a.x, nbytes, hipMemcpyDeviceToDevice, st))) != GNCA_OK) return rc;
+    return t_hip(hipMemcpyAsync(a.v_final, a.v, (size_t)K * nbytes, hipMemcpyDeviceToDevice, st));
+  }
+  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
+  char* step_ws = wsb + R.masks;
+  float* xp[2] = {nullptr, nullptr}, *vp[2];
+  for (int q = 0; q < 2; ++q) {
+    if (R.nstate) xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
+    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)R.nstate * R.state + (size_t)q * R.block);
+  }
+  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
+    return rc;
+  const float* xc = a.x;
+  if (a.tape) {   // the tape stands alone: slot 0 keeps its own copy of x, and step 0 reads it there
+    if ((rc = t_hip(hipMemcpyAsync(a.tape, a.x, nbytes, hipMemcpyDeviceToDevice, st))) != GNCA_OK) return rc;
+    xc = reinterpret_cast<const float*>(a.tape);
+  }
+  const float* vc = a.v;
+  if (!vc) {   // the zero block: step 0 reads vp[1] and writes vp[0]
+    const size_t nv = R.block / sizeof(float4);
+    hipLaunchKernelGGL(gnca_t_zero_v4, dim3((unsigned)std::min<size_t>((nv + kThreads - 1) / kThreads, 4096)),
+                       dim3(kThreads), 0, st, reinterpret_cast<float4*>(vp[1]), nv);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+    vc = vp[1];
+  }
+  if (a.carry) {
+    hipLaunchKernelGGL(gnca_t_zero_f64, dim3((unsigned)((a.ncarry + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       a.carry, a.ncarry);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+  }
+  for (int t = 0; t < T; ++t) {
+    gnca_step_desc sd;
+    sched_step_desc(desc, sched, t, &sd);
+    float* xn;
+    if (t == T - 1) xn = a.x_final;
+    else if (!a.tape) xn = xp[t & 1];
+    else if (a.every == 0) xn = reinterpret_cast<float*>(a.tape + (size_t)(t + 1) * a.slot);
+    else xn = (t + 1) % a.every == 0 ? reinterpret_cast<float*>(a.tape + (size_t)((t + 1) / a.every) * a.slot)
+                                     : xp[t & 1];
+    float* vn = (t == T - 1 && a.v_final) ? a.v_final : vp[t & 1];
+    const void* fire = sched_step_fire(desc, sched, t);
+    const uint8_t* active = sched_step_active(desc, sched, t, masks);
+    if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
+    for (int j = 0; j < K; ++j)
+      if ((rc = step_tangent_dir(&sd, w, a.dw ? a.dw + j : nullptr, xc, fire, active, vc + (size_t)j * dstride, xn,
+                                 vn + (size_t)j * dstride, step_ws, st)) != GNCA_OK)
+        return rc;
+    xc = xn;
+    vc = vn;
+    if ((rc = after(t, xn, vn)) != GNCA_OK) return rc;
+  }
+  return GNCA_OK;
 }
 
 }  // namespace
@@ -1206,10 +1292,7 @@ static int step_tangent_entry(const gnca_step_desc* desc, const gnca_weights* w,
                               const float* x, const void* fire, const uint8_t* active, const float* v, float* x_out,
                               float* v_out, void* ws, size_t ws_bytes, void* hip_stream) {
   if (!desc || !w || !x || !v || !x_out || !v_out) return GNCA_ERR_INVALID;
-  const void* ptrs[] = {x, x_out, v_out};
-  const void* ptrs2[] = {v, x_out, v_out};
-  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
-  if (dw && dir_aliases(dw, 1, x_out, v_out)) return GNCA_ERR_INVALID;
+  if (!outputs_distinct({x_out, v_out}, x, v, dw, 1)) return GNCA_ERR_INVALID;
   if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
   TanLayout T;
   if (!tan_layout(desc, &T)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
@@ -1233,9 +1316,9 @@ int gnca_step_tangent_params(const gnca_step_desc* desc, const gnca_weights* w, 
 
 size_t gnca_rollout_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
                                             const gnca_tangent_args* args) {
-  RollTanLayout R;
-  if (!desc || !sched || !args || tangent_unsupported(desc)) return 0;
-  return roll_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
+  RollTanLayout L;
+  if (!desc || !sched || !args) return 0;
+  return roll_tan_layout(desc, sched, args, &L) ? L.bytes : 0;
 }
 
 // the body of gnca_rollout_tangent (dw == NULL) and of gnca_rollout_tangent_params
@@ -1243,83 +1326,38 @@ static int rollout_tangent_entry(const gnca_step_desc* desc, const gnca_weights*
                                  const gnca_rollout_sched* sched, const gnca_tangent_args* args, const float* x,
                                  const float* v, float* x_final, float* v_final, void* ws, size_t ws_bytes) {
   if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
-  const void* ptrs[] = {x, x_final, v_final};
-  const void* ptrs2[] = {v, x_final, v_final};
-  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
-  if (dw && dir_aliases(dw, 1, x_final, v_final)) return GNCA_ERR_INVALID;
+  if (!outputs_distinct({x_final, v_final}, x, v, dw, 1)) return GNCA_ERR_INVALID;
   // rescaling v alone breaks linearity in the pair (v, dtheta)
   if (dw && (args->flags & GNCA_TANGENT_RENORM)) return GNCA_ERR_INVALID;
-  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
-  if (!sched_ok(desc, sched) || !records_ok(sched, args)) return GNCA_ERR_INVALID;
-  if (args->num_records > 0 && !args->log_norm) return GNCA_ERR_INVALID;
-  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
-  RollTanLayout R;
-  if (!roll_tan_layout(desc, sched, args, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
-  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
-  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && sched->steps > 0 &&
-      !sched->fire)
-    return GNCA_ERR_INVALID;
+  if (!records_ok(sched, args) || (args->num_records > 0 && !args->log_norm)) return GNCA_ERR_INVALID;
+  RollTanLayout L;
+  const bool laid = roll_tan_layout(desc, sched, args, &L);
+  int rc = tan_roll_check(desc, sched, false, laid, laid && ws && ws_bytes >= L.bytes);
+  if (rc != GNCA_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(args->stream);
   StreamDeviceGuard dg(st);
-  const int T = sched->steps, B = desc->B;
-  const size_t n = (size_t)desc->C * desc->H * desc->W, nbytes = (size_t)B * n * sizeof(float);
+  const int B = desc->B;
+  const size_t n = (size_t)desc->C * desc->H * desc->W;
   char* wsb = reinterpret_cast<char*>(ws);
-  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
-  char* step_ws = wsb + R.masks;
-  float* xp[2], *vp[2];
-  for (int q = 0; q < 2; ++q) {
-    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
-    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)(2 + q) * R.state);
-  }
-  double* pn = reinterpret_cast<double*>(wsb + R.off_pn);
-  double* carry = reinterpret_cast<double*>(wsb + R.off_carry);
-  float* scale = reinterpret_cast<float*>(wsb + R.off_scale);
-  int rc;
-  if (T == 0) {
-    hipError_t e = hipMemcpyAsync(x_final, x, nbytes, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(v_final, v, nbytes, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) {
-      g_last_hip = (int)e;
-      return GNCA_ERR_HIP;
-    }
-    return GNCA_OK;
-  }
-  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
-    return rc;
-  if (args->num_records > 0) {
-    hipLaunchKernelGGL(gnca_t_zero_f64, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, carry,
-                       B);
-    if ((rc = t_check()) != GNCA_OK) return rc;
-  }
-  const float* xc = x;
-  const float* vc = v;
+  double* pn = reinterpret_cast<double*>(wsb + L.off_pn);
+  double* carry = reinterpret_cast<double*>(wsb + L.off_carry);
+  float* scale = reinterpret_cast<float*>(wsb + L.off_scale);
+  const TanRoll roll = {1, dw, x, v, x_final, v_final, nullptr, 0, 0, args->num_records > 0 ? carry : nullptr, B};
   int r = 0;
-  for (int t = 0; t < T; ++t) {
-    gnca_step_desc sd;
-    sched_step_desc(desc, sched, t, &sd);
-    float* xn = t == T - 1 ? x_final : xp[t & 1];
-    float* vn = t == T - 1 ? v_final : vp[t & 1];
-    rc = step_tangent_impl(&sd, w, dw, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks), vc,
-                           xn, vn, step_ws, R.step_ws, st);
-    if (rc != GNCA_OK) return rc;
-    xc = xn;
-    vc = vn;
-    if (r < args->num_records && args->record[r] == t + 1) {
-      const dim3 g((unsigned)R.nchunk, (unsigned)B);
-      const int renorm = (args->flags & GNCA_TANGENT_RENORM) ? 1 : 0;
-      hipLaunchKernelGGL(gnca_t_sumsq, g, dim3(kThreads), 0, st, (const float*)vn, pn, n, R.nchunk);
-      if ((rc = t_check()) != GNCA_OK) return rc;
-      hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, R.nchunk, carry,
-                         scale, args->log_norm + (size_t)r * B, renorm, 1);
-      if ((rc = t_check()) != GNCA_OK) return rc;
-      if (renorm) {
-        hipLaunchKernelGGL(gnca_t_scale, g, dim3(kThreads), 0, st, vn, (const float*)scale, n);
-        if ((rc = t_check()) != GNCA_OK) return rc;
-      }
-      ++r;
-    }
-  }
-  return GNCA_OK;
+  return tangent_rollout(desc, w, sched, L.R, wsb, roll, st, [&](int t, float*, float* vn) {
+    if (r >= args->num_records || args->record[r] != t + 1) return (int)GNCA_OK;
+    const dim3 g((unsigned)L.nchunk, (unsigned)B);
+    const int renorm = (args->flags & GNCA_TANGENT_RENORM) ? 1 : 0;
+    hipLaunchKernelGGL(gnca_t_sumsq, g, dim3(kThreads), 0, st, (const float*)vn, pn, n, L.nchunk);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+    hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, L.nchunk, carry, scale,
+                       args->log_norm + (size_t)r * B, renorm, 1);
+    if ((rc = t_check()) != GNCA_OK) return rc;
+    ++r;
+    if (!renorm) return (int)GNCA_OK;
+    hipLaunchKernelGGL(gnca_t_scale, g, dim3(kThreads), 0, st, vn, (const float*)scale, n);
+    return t_check();
+  });
 }
 
 int gnca_rollout_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
@@ -1353,9 +1391,9 @@ int gnca_tangent_qr(int32_t num_dirs, int32_t B, int64_t n, float* v, double* r,
 
 size_t gnca_rollout_tangent_block_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
                                                   const gnca_tangent_block_args* args) {
-  BlockTanLayout R;
-  if (!desc || !sched || !args || tangent_unsupported(desc)) return 0;
-  return block_tan_layout(desc, sched, args, &R) ? R.bytes : 0;
+  BlockTanLayout L;
+  if (!desc || !sched || !args) return 0;
+  return block_tan_layout(desc, sched, args, &L) ? L.bytes : 0;
 }
 
 // the body of gnca_rollout_tangent_block (dw == NULL) and of gnca_rollout_tangent_block_params (dw [K])
@@ -1364,90 +1402,40 @@ static int rollout_tangent_block_entry(const gnca_step_desc* desc, const gnca_we
                                        const float* x, const float* v, float* x_final, float* v_final, void* ws,
                                        size_t ws_bytes) {
   if (!desc || !w || !sched || !args || !x || !v || !x_final || !v_final) return GNCA_ERR_INVALID;
-  const void* ptrs[] = {x, x_final, v_final};
-  const void* ptrs2[] = {v, x_final, v_final};
-  if (!distinct(ptrs, 3) || !distinct(ptrs2, 3)) return GNCA_ERR_INVALID;
-  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
-  if (!sched_ok(desc, sched) || !block_records_ok(sched, args)) return GNCA_ERR_INVALID;
+  if (!block_records_ok(sched, args) || (args->num_records > 0 && !args->log_r)) return GNCA_ERR_INVALID;
+  if (!outputs_distinct({x_final, v_final}, x, v, dw, args->num_dirs)) return GNCA_ERR_INVALID;
   // mixing the v_j alone breaks linearity in the pairs (v_j, dtheta_j)
   if (dw && (args->flags & GNCA_TBLOCK_ORTHO)) return GNCA_ERR_INVALID;
-  if (dw && dir_aliases(dw, args->num_dirs, x_final, v_final)) return GNCA_ERR_INVALID;
-  if (args->num_records > 0 && !args->log_r) return GNCA_ERR_INVALID;
-  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
-  BlockTanLayout R;
-  if (!block_tan_layout(desc, sched, args, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
-  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
-  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && sched->steps > 0 &&
-      !sched->fire)
-    return GNCA_ERR_INVALID;
+  BlockTanLayout L;
+  const bool laid = block_tan_layout(desc, sched, args, &L);
+  int rc = tan_roll_check(desc, sched, false, laid, laid && ws && ws_bytes >= L.bytes);
+  if (rc != GNCA_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(args->stream);
   StreamDeviceGuard dg(st);
-  const int T = sched->steps, B = desc->B, K = args->num_dirs;
-  const size_t n = (size_t)desc->C * desc->H * desc->W, dstride = (size_t)B * n, nbytes = dstride * sizeof(float);
+  const int B = desc->B, K = args->num_dirs;
+  const size_t n = (size_t)desc->C * desc->H * desc->W, dstride = (size_t)B * n;
   char* wsb = reinterpret_cast<char*>(ws);
-  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
-  char* step_ws = wsb + R.masks;
-  float* xp[2], *vp[2];
-  for (int q = 0; q < 2; ++q) {
-    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
-    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + 2 * R.state + (size_t)q * R.block);
-  }
-  double* pn = reinterpret_cast<double*>(wsb + R.off_pn);
-  float* scale = reinterpret_cast<float*>(wsb + R.off_scale);
-  double* carry = reinterpret_cast<double*>(wsb + R.off_carry);
-  int rc;
-  if (T == 0) {
-    hipError_t e = hipMemcpyAsync(x_final, x, nbytes, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(v_final, v, (size_t)K * nbytes, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) {
-      g_last_hip = (int)e;
-      return GNCA_ERR_HIP;
-    }
-    return GNCA_OK;
-  }
-  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
-    return rc;
-  if (args->num_records > 0) {   // (without ORTHO the first B entries serve every direction and stay zero)
-    hipLaunchKernelGGL(gnca_t_zero_f64, dim3((unsigned)((B * K + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       carry, B * K);
-    if ((rc = t_check()) != GNCA_OK) return rc;
-  }
+  double* pn = reinterpret_cast<double*>(wsb + L.off_pn);
+  float* scale = reinterpret_cast<float*>(wsb + L.off_scale);
+  double* carry = reinterpret_cast<double*>(wsb + L.off_carry);
   const bool ortho = (args->flags & GNCA_TBLOCK_ORTHO) != 0;
-  const float* xc = x;
-  const float* vc = v;
+  // (without ORTHO the first B carries serve every direction and stay zero)
+  const TanRoll roll = {K, dw, x, v, x_final, v_final, nullptr, 0, 0, args->num_records > 0 ? carry : nullptr, B * K};
   int r = 0;
-  for (int t = 0; t < T; ++t) {
-    gnca_step_desc sd;
-    sched_step_desc(desc, sched, t, &sd);
-    float* xn = t == T - 1 ? x_final : xp[t & 1];
-    float* vn = t == T - 1 ? v_final : vp[t & 1];
-    const void* fire = sched_step_fire(desc, sched, t);
-    const uint8_t* active = sched_step_active(desc, sched, t, masks);
-    if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
-    for (int j = 0; j < K; ++j)
-      if ((rc = step_tangent_dir(&sd, w, dw ? dw + j : nullptr, xc, fire, active, vc + (size_t)j * dstride, xn,
-                                 vn + (size_t)j * dstride, step_ws, st)) != GNCA_OK)
-        return rc;
-    xc = xn;
-    vc = vn;
-    if (r < args->num_records && args->record[r] == t + 1) {
-      double* out = args->log_r + (size_t)r * B * K;
-      if (ortho) {
-        if ((rc = launch_qr(R.Q, K, B, n, dstride, vn, nullptr, out, carry, wsb + R.off_qr, st)) != GNCA_OK) return rc;
-      } else {
-        for (int j = 0; j < K; ++j) {
-          hipLaunchKernelGGL(gnca_t_sumsq, dim3((unsigned)R.nchunk, (unsigned)B), dim3(kThreads), 0, st,
-                             (const float*)(vn + (size_t)j * dstride), pn, n, R.nchunk);
-          if ((rc = t_check()) != GNCA_OK) return rc;
-          hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, R.nchunk, carry,
-                             scale, out + j, 0, K);
-          if ((rc = t_check()) != GNCA_OK) return rc;
-        }
-      }
-      ++r;
+  return tangent_rollout(desc, w, sched, L.R, wsb, roll, st, [&](int t, float*, float* vn) {
+    if (r >= args->num_records || args->record[r] != t + 1) return (int)GNCA_OK;
+    double* out = args->log_r + (size_t)r++ * B * K;
+    if (ortho) return launch_qr(L.Q, K, B, n, dstride, vn, nullptr, out, carry, wsb + L.off_qr, st);
+    for (int j = 0; j < K; ++j) {
+      hipLaunchKernelGGL(gnca_t_sumsq, dim3((unsigned)L.nchunk, (unsigned)B), dim3(kThreads), 0, st,
+                         (const float*)(vn + (size_t)j * dstride), pn, n, L.nchunk);
+      if ((rc = t_check()) != GNCA_OK) return rc;
+      hipLaunchKernelGGL(gnca_t_lognorm, dim3((unsigned)B), dim3(64), 0, st, (const double*)pn, L.nchunk, carry,
+                         scale, out + j, 0, K);
+      if ((rc = t_check()) != GNCA_OK) return rc;
     }
-  }
-  return GNCA_OK;
+    return (int)GNCA_OK;
+  });
 }
 
 int gnca_rollout_tangent_block(const gnca_step_desc* desc, const gnca_weights* w, const gnca_rollout_sched* sched,
@@ -1466,13 +1454,12 @@ int gnca_rollout_tangent_block_params(const gnca_step_desc* desc, const gnca_wei
 
 size_t gnca_rollout_objective_tangent_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
                                                       const gnca_rollout_taps* taps, int32_t num_dirs) {
-  ObjTanLayout R;
-  if (!desc || !sched || !taps || tangent_unsupported(desc)) return 0;
+  TanRollLayout R;
+  if (!desc || !sched || !taps) return 0;
   return obj_tan_layout(desc, sched, taps, num_dirs, &R) ? R.bytes : 0;
 }
 
-// rollout_tangent_block_entry's loop without the QR branch and the log norms; after a tapped step has written
-// (xn, vn), gnca_tap_loss_tangent reads them in place
+// after a tapped step has written (xn, vn), gnca_tap_loss_tangent reads them in place
 int gnca_rollout_objective_tangent(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
                                    const gnca_rollout_sched* sched, const gnca_rollout_taps* taps, int32_t num_dirs,
                                    const float* x, const float* v, float* x_final, float* v_final, float* losses,
@@ -1480,88 +1467,36 @@ int gnca_rollout_objective_tangent(const gnca_step_desc* desc, const gnca_weight
   if (!desc || !w || !sched || !taps || !x || !x_final || !losses || !dlosses) return GNCA_ERR_INVALID;
   if (!v && !dw) return GNCA_ERR_INVALID;
   if (num_dirs < 1 || num_dirs > kMaxDirs) return GNCA_ERR_INVALID;
-  {
-    const void* outs[5] = {x_final, losses, dlosses, v_final, alive_count};
-    for (int i = 0; i < 5; ++i) {
-      if (!outs[i]) continue;
-      if (outs[i] == x || outs[i] == v) return GNCA_ERR_INVALID;
-      for (int j = i + 1; j < 5; ++j)
-        if (outs[i] == outs[j]) return GNCA_ERR_INVALID;
-    }
-    if (dw && (dir_aliases(dw, num_dirs, x_final, v_final) || dir_aliases(dw, num_dirs, losses, dlosses)))
-      return GNCA_ERR_INVALID;
-  }
-  if (sched->flags & (GNCA_SCHED_RECOMPUTE | GNCA_SCHED_CHECKPOINT)) return GNCA_ERR_INVALID;   // there is no tape
-  if (!sched_ok(desc, sched) || !taps_ok(desc, sched, taps)) return GNCA_ERR_INVALID;
-  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
-  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
-  ObjTanLayout R;
-  if (!obj_tan_layout(desc, sched, taps, num_dirs, &R))
-    return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
-  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
-  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && !sched->fire)
-    return GNCA_ERR_INVALID;
+  if (!outputs_distinct({x_final, losses, dlosses, v_final, alive_count}, x, v, dw, num_dirs)) return GNCA_ERR_INVALID;
+  if (!taps_ok(desc, sched, taps) || (taps->kind == GNCA_TAP_MASKED && !alive_count)) return GNCA_ERR_INVALID;
+  TanRollLayout R;
+  const bool laid = obj_tan_layout(desc, sched, taps, num_dirs, &R);
+  const int rc = tan_roll_check(desc, sched, false, laid, laid && ws && ws_bytes >= R.bytes);
+  if (rc != GNCA_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(taps->stream);
   StreamDeviceGuard dg(st);
-  const int T = sched->steps, B = desc->B, K = num_dirs;   // (T >= 1: a tap list is never empty)
+  const int B = desc->B, K = num_dirs;   // (steps >= 1: a tap list is never empty)
   const size_t n = (size_t)desc->C * desc->H * desc->W, dstride = (size_t)B * n;
-  char* wsb = reinterpret_cast<char*>(ws);
-  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
-  char* step_ws = wsb + R.masks;
-  float* xp[2], *vp[2];
-  for (int q = 0; q < 2; ++q) {
-    xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
-    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + 2 * R.state + (size_t)q * R.block);
-  }
-  int rc;
-  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
-    return rc;
-  const float* xc = x;
-  const float* vc = v;
-  if (!v) {   // the zero block: step 0 reads vp[1] and writes vp[0]
-    const hipError_t e = hipMemsetAsync(vp[1], 0, (size_t)K * dstride * sizeof(float), st);
-    if (e != hipSuccess) {
-      g_last_hip = (int)e;
-      return GNCA_ERR_HIP;
-    }
-    vc = vp[1];
-  }
+  const TanRoll roll = {K, dw, x, v, x_final, v_final, nullptr, 0, 0, nullptr, 0};
   int r = 0;
-  for (int t = 0; t < T; ++t) {
-    gnca_step_desc sd;
-    sched_step_desc(desc, sched, t, &sd);
-    float* xn = t == T - 1 ? x_final : xp[t & 1];
-    float* vn = (t == T - 1 && v_final) ? v_final : vp[t & 1];
-    const void* fire = sched_step_fire(desc, sched, t);
-    const uint8_t* active = sched_step_active(desc, sched, t, masks);
-    if ((rc = step_tangent_primal(&sd, w, xc, fire, active, xn, step_ws, R.step_ws, st)) != GNCA_OK) return rc;
-    for (int j = 0; j < K; ++j)
-      if ((rc = step_tangent_dir(&sd, w, dw ? dw + j : nullptr, xc, fire, active, vc + (size_t)j * dstride, xn,
-                                 vn + (size_t)j * dstride, step_ws, st)) != GNCA_OK)
-        return rc;
-    xc = xn;
-    vc = vn;
-    if (r < taps->n && taps->steps[r] == t + 1) {
-      rc = launch_tap_loss_tangent(taps->kind, &taps->masked, K, xn, n, vn, dstride, n, taps->target,
-                                   (long)taps->target_bstride, losses + (size_t)r * B, dlosses + (size_t)r * K * B,
-                                   r == 0 ? alive_count : nullptr, st);
-      if (rc != GNCA_OK) return rc;
-      ++r;
-    }
-  }
-  return GNCA_OK;
+  return tangent_rollout(desc, w, sched, R, reinterpret_cast<char*>(ws), roll, st, [&](int t, float* xn, float* vn) {
+    if (r >= taps->n || taps->steps[r] != t + 1) return (int)GNCA_OK;
+    const int q = r++;
+    return launch_tap_loss_tangent(taps->kind, &taps->masked, K, xn, n, vn, dstride, n, taps->target,
+                                   (long)taps->target_bstride, losses + (size_t)q * B, dlosses + (size_t)q * K * B,
+                                   q == 0 ? alive_count : nullptr, st);
+  });
 }
 
 size_t gnca_rollout_gn_fwd_workspace_bytes(const gnca_step_desc* desc, const gnca_rollout_sched* sched,
                                            const gnca_rollout_taps* taps) {
-  GnFwdLayout R;
-  if (!desc || !sched || !taps || tangent_unsupported(desc)) return 0;
-  return gn_fwd_layout(desc, sched, taps, &R) ? R.bytes : 0;
+  GnFwdLayout L;
+  if (!desc || !sched || !taps) return 0;
+  return gn_fwd_layout(desc, sched, taps, &L) ? L.R.bytes : 0;
 }
 
-// gnca_rollout_objective_tangent's loop for one direction with the primal's states written where
-// gnca_rollout_fwd_f32 writes them on a states-only tape; after a tapped step has written (xn, vn),
-// gnca_tap_curvature reads them in place
+// one direction, with the primal's states written where gnca_rollout_fwd_f32 writes them on a states-only tape;
+// after a tapped step has written (xn, vn), gnca_tap_curvature reads them in place
 int gnca_rollout_gn_fwd(const gnca_step_desc* desc, const gnca_weights* w, const gnca_weights* dw,
                         const gnca_rollout_sched* sched, const gnca_rollout_taps* taps, const float* x, const float* v,
                         float* x_final, void* tape, size_t tape_bytes, float* fields, float* losses, double* dlosses,
@@ -1569,78 +1504,27 @@ int gnca_rollout_gn_fwd(const gnca_step_desc* desc, const gnca_weights* w, const
   if (!desc || !w || !sched || !taps || !x || !x_final || !tape || !fields || !losses || !dlosses || !quad)
     return GNCA_ERR_INVALID;
   if (!v && !dw) return GNCA_ERR_INVALID;
-  {
-    const void* outs[7] = {x_final, tape, fields, losses, dlosses, quad, alive_count};
-    for (int i = 0; i < 7; ++i) {
-      if (!outs[i]) continue;
-      if (outs[i] == x || outs[i] == v) return GNCA_ERR_INVALID;
-      for (int j = i + 1; j < 7; ++j)
-        if (outs[i] == outs[j]) return GNCA_ERR_INVALID;
-    }
-    if (dw && (dir_aliases(dw, 1, x_final, tape) || dir_aliases(dw, 1, fields, losses) ||
-               dir_aliases(dw, 1, dlosses, quad) || (alive_count && dir_aliases(dw, 1, alive_count, alive_count))))
-      return GNCA_ERR_INVALID;
-  }
-  if (!(sched->flags & GNCA_SCHED_RECOMPUTE)) return GNCA_ERR_INVALID;   // the tape holds states only
-  if (!sched_ok(desc, sched) || !taps_ok(desc, sched, taps)) return GNCA_ERR_INVALID;
-  if (taps->kind == GNCA_TAP_MASKED && !alive_count) return GNCA_ERR_INVALID;
-  if (tangent_unsupported(desc)) return GNCA_ERR_UNSUPPORTED;
-  GnFwdLayout R;
-  if (!gn_fwd_layout(desc, sched, taps, &R)) return outside_support(desc) ? GNCA_ERR_UNSUPPORTED : GNCA_ERR_INVALID;
-  if (tape_bytes < R.T.bytes) return GNCA_ERR_WORKSPACE;
-  if (!ws || ws_bytes < R.bytes) return GNCA_ERR_WORKSPACE;
-  if ((desc->fire_mode == GNCA_FIRE_RAND_F32 || desc->fire_mode == GNCA_FIRE_MASK_U8) && !sched->fire)
+  if (!outputs_distinct({x_final, tape, fields, losses, dlosses, quad, alive_count}, x, v, dw, 1))
     return GNCA_ERR_INVALID;
+  if (!taps_ok(desc, sched, taps) || (taps->kind == GNCA_TAP_MASKED && !alive_count)) return GNCA_ERR_INVALID;
+  GnFwdLayout L;
+  const bool laid = gn_fwd_layout(desc, sched, taps, &L);
+  const int rc = tan_roll_check(desc, sched, true, laid,
+                                laid && tape_bytes >= L.T.bytes && ws && ws_bytes >= L.R.bytes);
+  if (rc != GNCA_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(taps->stream);
   StreamDeviceGuard dg(st);
-  const int T = sched->steps, B = desc->B, k = R.T.k;   // (T >= 1: a tap list is never empty)
-  const size_t HW = (size_t)desc->H * desc->W, n = (size_t)desc->C * HW, nbytes = (size_t)B * n * sizeof(float);
-  char* wsb = reinterpret_cast<char*>(ws);
-  char* tp = reinterpret_cast<char*>(tape);
-  uint8_t* masks = reinterpret_cast<uint8_t*>(wsb);
-  char* step_ws = wsb + R.masks;
-  float* xp[2] = {nullptr, nullptr}, *vp[2];
-  for (int q = 0; q < 2; ++q) {
-    if (R.nstate) xp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)q * R.state);
-    vp[q] = reinterpret_cast<float*>(wsb + R.masks + R.step_ws + (size_t)(R.nstate + q) * R.state);
-  }
-  int rc;
-  if (sched->nsteps && (rc = launch_nsteps_masks(sched->nsteps, B, T, sched->full_steps, masks, st)) != GNCA_OK)
-    return rc;
-  // the tape stands alone: slot 0 keeps its own copy of x, and step 0 reads it there
-  if (hipMemcpyAsync(tp, x, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return GNCA_ERR_HIP;
-  const float* xc = reinterpret_cast<const float*>(tp);
-  const float* vc = v;
-  if (!v) {   // the zero tangent: step 0 reads vp[1] and writes vp[0]
-    const size_t nv = R.state / sizeof(float4);
-    hipLaunchKernelGGL(gnca_t_zero_v4, dim3((unsigned)std::min<size_t>((nv + kThreads - 1) / kThreads, 4096)),
-                       dim3(kThreads), 0, st, reinterpret_cast<float4*>(vp[1]), nv);
-    if ((rc = t_check()) != GNCA_OK) return rc;
-    vc = vp[1];
-  }
+  const int B = desc->B;   // (steps >= 1: a tap list is never empty)
+  const size_t HW = (size_t)desc->H * desc->W, n = (size_t)desc->C * HW;
+  const TanRoll roll = {1, dw, x, v, x_final, nullptr, reinterpret_cast<char*>(tape), L.T.slot, L.T.k, nullptr, 0};
   int r = 0;
-  for (int t = 0; t < T; ++t) {
-    gnca_step_desc sd;
-    sched_step_desc(desc, sched, t, &sd);
-    float* xn;
-    if (t == T - 1) xn = x_final;
-    else if (k == 0) xn = reinterpret_cast<float*>(tp + (size_t)(t + 1) * R.T.slot);
-    else xn = (t + 1) % k == 0 ? reinterpret_cast<float*>(tp + (size_t)((t + 1) / k) * R.T.slot) : xp[t & 1];
-    float* vn = vp[t & 1];
-    rc = step_tangent_impl(&sd, w, dw, xc, sched_step_fire(desc, sched, t), sched_step_active(desc, sched, t, masks),
-                           vc, xn, vn, step_ws, R.step_ws, st);
-    if (rc != GNCA_OK) return rc;
-    xc = xn;
-    vc = vn;
-    if (r < taps->n && taps->steps[r] == t + 1) {
-      rc = launch_tap_curvature(taps->kind, &taps->masked, xn, n, vn, n, taps->target, (long)taps->target_bstride,
-                                losses + (size_t)r * B, dlosses + (size_t)r * B, quad + (size_t)r * B,
-                                fields + (size_t)r * B * 4 * HW, 4 * HW, r == 0 ? alive_count : nullptr, st);
-      if (rc != GNCA_OK) return rc;
-      ++r;
-    }
-  }
-  return GNCA_OK;
+  return tangent_rollout(desc, w, sched, L.R, reinterpret_cast<char*>(ws), roll, st, [&](int t, float* xn, float* vn) {
+    if (r >= taps->n || taps->steps[r] != t + 1) return (int)GNCA_OK;
+    const int q = r++;
+    return launch_tap_curvature(taps->kind, &taps->masked, xn, n, vn, n, taps->target, (long)taps->target_bstride,
+                                losses + (size_t)q * B, dlosses + (size_t)q * B, quad + (size_t)q * B,
+                                fields + (size_t)q * B * 4 * HW, 4 * HW, q == 0 ? alive_count : nullptr, st);
+  });
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 """Shared forward of NeuralCA / NeuralCAGraph: descriptor + weights -> one HIP step."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import random
 import weakref
 
 import torch
@@ -366,12 +368,9 @@ def run_rollout(model: nn.Module, x: torch.Tensor, steps: int, graph, hidden_onl
     return out
 
 
-def run_rollout_memory(model: nn.Module, x_or_shape, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
-                       message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0,
-                       offsets=None, recompute=False, checkpoint_every=None) -> dict:
-    """The shared body of ``rollout_memory``: the schedule ``rollout()`` would build for these
-    arguments, asked for its sizes.  Host-only; Python's and torch's RNG states are put back."""
-    import random
+def _shape_and_device(model: nn.Module, x_or_shape, nsteps, fire):
+    """(shape, device) of a state given as a tensor or as its shape (then the device of ``nsteps`` or ``fire``,
+    else the CPU); ValueError unless it is a [B,C,H,W] of the model's channel count."""
     if isinstance(x_or_shape, torch.Tensor):
         shape, device = tuple(x_or_shape.shape), x_or_shape.device
     else:
@@ -382,20 +381,58 @@ def run_rollout_memory(model: nn.Module, x_or_shape, steps: int, graph, hidden_o
         raise ValueError(f"state must be [B,C,H,W], got {shape}")
     if shape[1] != model.n_channels:
         raise ValueError(f"state has {shape[1]} channels, model expects {model.n_channels}")
-    B, C, H, W = shape
-    _check_norm(model)
+    return shape, device
+
+
+@contextlib.contextmanager
+def _rng_restored():
+    """Python's and torch's CPU RNG states are put back on the way out."""
     py_state, torch_state = random.getstate(), torch.get_rng_state()
     try:
+        yield
+    finally:
+        random.setstate(py_state)
+        torch.set_rng_state(torch_state)
+
+
+def _steps_int(steps, minimum: int) -> None:
+    """ValueError unless ``steps`` is an int >= ``minimum`` (0 or 1)."""
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < minimum:
+        raise ValueError(f"steps must be a {'positive' if minimum else 'non-negative'} int, got {steps!r}")
+
+
+def run_rollout_memory(model: nn.Module, x_or_shape, steps: int, graph, hidden_only: bool, *, fire_rate=1.0,
+                       message_gain=None, nsteps=None, min_steps=0, fire=None, seed=None, sample_base=0,
+                       offsets=None, recompute=False, checkpoint_every=None) -> dict:
+    """The shared body of ``rollout_memory``: the schedule ``rollout()`` would build for these
+    arguments, asked for its sizes.  Host-only; Python's and torch's RNG states are put back."""
+    shape, device = _shape_and_device(model, x_or_shape, nsteps, fire)
+    B, C, H, W = shape
+    _check_norm(model)
+    with _rng_restored():
         sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=device, fire_rate=fire_rate,
                                  message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
                                  seed=seed, sample_base=sample_base, offsets=offsets,
                                  sample_offsets=None if graph is None else graph.sample_offsets,
                                  recompute=recompute, checkpoint_every=checkpoint_every)
-    finally:
-        random.setstate(py_state)
-        torch.set_rng_state(torch_state)
     desc, _ = _rollout_desc_host(model, shape, steps, graph, hidden_only, sched)
     return S.RolloutCall(desc, sched).memory()
+
+
+def _tap_knobs(loss: str, alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb):
+    """The masked tap loss's four numbers, checked (ValueError), or None for the premultiplied kind."""
+    from .. import loss as LS
+    if loss != "masked":
+        return None
+    return (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
+            LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
+
+
+def _tap_target(target: torch.Tensor, device) -> torch.Tensor:
+    """The prepared target as the kernels read it: float32, contiguous, on ``device``; one sample when it is
+    broadcast over the batch."""
+    tgt = target.detach().to(device, torch.float32)
+    return tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
 
 
 class _RolloutObjectiveFn(torch.autograd.Function):
@@ -485,12 +522,8 @@ def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target,
     if C < 4:
         raise ValueError(f"the losses read channels 0..3 of the state, which has {C}")
     _, target = LS._prepare(x[:, :4], target)
-    knobs = None
-    if loss == "masked":
-        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
-                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    knobs = _tap_knobs(loss, alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb)
+    _steps_int(steps, 1)
     rec = S.expand_record(steps, every, record)
     if not rec:
         raise ValueError("record is empty: a rollout objective needs at least one tapped step")
@@ -505,8 +538,7 @@ def run_rollout_objective(model: nn.Module, x: torch.Tensor, steps: int, target,
                              sample_offsets=None if graph is None else graph.sample_offsets,
                              recompute=recompute if grad else True, checkpoint_every=checkpoint_every)
     desc, w, keep, tensors = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-    tgt = target.detach().to(x.device, torch.float32)
-    tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
+    tgt = _tap_target(target, x.device)
     call, taps = S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt)
     if grad:
         core, gpack = param_packs(model, tensors)
@@ -723,6 +755,36 @@ def _direction_weights(fields: dict):
     return S.make_weights({k: t.detach() for k, t in fields.items()})
 
 
+def _check_dparams_block(model: nn.Module, dparams, allow_single: bool) -> list:
+    """``_check_dparams`` of each of the K directions of a block; ``allow_single``: one dict stands for K = 1."""
+    if allow_single and isinstance(dparams, dict):
+        dparams = [dparams]
+    if not isinstance(dparams, (list, tuple)) or not 1 <= len(dparams) <= L.TANGENT_MAX_DIRS:
+        raise ValueError(f"dparams must be a {'dict or a ' if allow_single else ''}list of K dicts, "
+                         f"1 <= K <= {L.TANGENT_MAX_DIRS}")
+    return [_check_dparams(model, d) for d in dparams]
+
+
+def _direction_block(dfields):
+    """(K Weights structs, their tensors to keep alive) of a checked block of directions, or (None, None)."""
+    if dfields is None:
+        return None, None
+    pairs = [_direction_weights(f) for f in dfields]
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+def _draw_schedule(x, steps, graph, *, seed=None, offsets=None, **schedule_kw):
+    """``S.build_schedule`` for the state ``x``, with the graph's offsets drawn only once every other schedule
+    argument has passed (and before a seed is drawn): a rejected call leaves Python's and torch's generators
+    alone."""
+    B, _, H, W = x.shape
+    kw = dict(steps=steps, B=B, H=H, W=W, device=x.device, **schedule_kw)
+    if graph is not None and offsets is None:
+        S.build_schedule(seed=0 if seed is None else seed, offsets=[[] for _ in range(steps)], **kw)
+    return S.build_schedule(seed=seed, offsets=offsets,
+                            sample_offsets=None if graph is None else graph.sample_offsets, **kw)
+
+
 def run_tangent_step(model: nn.Module, x, v, fire_rate, graph, message_gain, hidden_only: bool, *, active=None,
                      offsets=None, fire=None, dparams=None):
     """The shared body of ``NeuralCA.tangent_step`` / ``NeuralCAGraph.tangent_step``."""
@@ -799,10 +861,8 @@ def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool,
         raise ValueError("v=None (a zero tangent) is allowed only together with dparams")
     _check_tangent_pair(model, x, x if v is None else v)
     dfields = None if dparams is None else _check_dparams(model, dparams)
-    B, C, H, W = x.shape
     _tangent_flags(model, graph, hidden_only)
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
-        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    _steps_int(steps, 0)
     if not isinstance(renormalize, bool):
         raise ValueError(f"renormalize must be a bool, got {renormalize!r}")
     if renormalize and dfields is not None:
@@ -813,16 +873,8 @@ def run_rollout_tangent(model: nn.Module, x, v, steps, graph, hidden_only: bool,
     with torch.no_grad():
         x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
         v = torch.zeros_like(x) if v is None else S._dev_f32(v.detach(), "tangent")
-        if graph is not None and offsets is None:
-            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
-            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
-                             seed=0 if seed is None else seed, sample_base=sample_base,
-                             offsets=[[] for _ in range(steps)])
-        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                 sample_base=sample_base, offsets=offsets,
-                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        sched = _draw_schedule(x, steps, graph, fire_rate=fire_rate, message_gain=message_gain, nsteps=nsteps,
+                               min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base, offsets=offsets)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
         dw, dkeep = (None, None) if dfields is None else _direction_weights(dfields)
         x_final, v_final, log_norm = S.rollout_tangent(S.RolloutCall(desc, sched), w, x, v, rec, renormalize,
@@ -862,9 +914,7 @@ def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only:
     """The shared body of ``NeuralCA.rollout_tangent_block`` / ``NeuralCAGraph.rollout_tangent_block``."""
     dfields = None
     if dparams is not None:
-        if not isinstance(dparams, (list, tuple)) or not 1 <= len(dparams) <= L.TANGENT_MAX_DIRS:
-            raise ValueError(f"dparams must be a list of K dicts, 1 <= K <= {L.TANGENT_MAX_DIRS}")
-        dfields = [_check_dparams(model, d) for d in dparams]
+        dfields = _check_dparams_block(model, dparams, allow_single=False)
         if isinstance(V, torch.Tensor) and V.dim() == 5 and V.shape[0] != len(dparams):
             raise ValueError(f"{len(dparams)} parameter directions for a block of {V.shape[0]} tangents")
         if orthonormalize is True:
@@ -882,31 +932,18 @@ def run_rollout_tangent_block(model: nn.Module, x, V, steps, graph, hidden_only:
     if not 1 <= V.shape[0] <= L.TANGENT_MAX_DIRS:
         raise ValueError(f"the block holds {V.shape[0]} directions; 1 <= K <= {L.TANGENT_MAX_DIRS}")
     _check_tangent_pair(model, x, V[0])
-    B, C, H, W = x.shape
     _tangent_flags(model, graph, hidden_only)
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
-        raise ValueError(f"steps must be a non-negative int, got {steps!r}")
+    _steps_int(steps, 0)
     if not isinstance(orthonormalize, bool):
         raise ValueError(f"orthonormalize must be a bool, got {orthonormalize!r}")
     rec = [] if every is None and record is None else S.expand_record(steps, 1 if every is None else every, record)
     with torch.no_grad():
         x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
         V = S._dev_f32(V.detach(), "tangent block")
-        if graph is not None and offsets is None:
-            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
-            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
-                             seed=0 if seed is None else seed, sample_base=sample_base,
-                             offsets=[[] for _ in range(steps)])
-        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                 sample_base=sample_base, offsets=offsets,
-                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        sched = _draw_schedule(x, steps, graph, fire_rate=fire_rate, message_gain=message_gain, nsteps=nsteps,
+                               min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base, offsets=offsets)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-        dws, dkeep = None, None
-        if dfields is not None:
-            pairs = [_direction_weights(f) for f in dfields]
-            dws, dkeep = [p[0] for p in pairs], [p[1] for p in pairs]
+        dws, dkeep = _direction_block(dfields)
         x_final, v_final, log_r = S.rollout_tangent_block(S.RolloutCall(desc, sched), w, x, V, rec, orthonormalize,
                                                           dweights=dws)
         del keep, dkeep
@@ -945,11 +982,7 @@ def run_rollout_objective_tangent(model: nn.Module, x, steps, target, graph, hid
         raise ValueError(f"state must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
     dfields = None
     if dparams is not None:
-        if isinstance(dparams, dict):
-            dparams = [dparams]
-        if not isinstance(dparams, (list, tuple)) or not 1 <= len(dparams) <= L.TANGENT_MAX_DIRS:
-            raise ValueError(f"dparams must be a dict or a list of K dicts, 1 <= K <= {L.TANGENT_MAX_DIRS}")
-        dfields = [_check_dparams(model, d) for d in dparams]
+        dfields = _check_dparams_block(model, dparams, allow_single=True)
     if V is not None:
         if not isinstance(V, torch.Tensor) or V.dim() != 5:
             raise ValueError(f"the tangent block must be [K,B,C,H,W], got {tuple(getattr(V, 'shape', ()))}")
@@ -959,17 +992,12 @@ def run_rollout_objective_tangent(model: nn.Module, x, steps, target, graph, hid
             raise ValueError(f"{len(dfields)} parameter directions for a block of {V.shape[0]} tangents")
     _check_tangent_pair(model, x, x if V is None else V[0])
     K = len(dfields) if V is None else V.shape[0]
-    B, C, H, W = x.shape
     _tangent_flags(model, graph, hidden_only)
     if loss not in S.TAP_KINDS:
         raise ValueError(f"loss must be one of {sorted(S.TAP_KINDS)}, got {loss!r}")
     _, target = LS._prepare(x[:, :4], target)
-    knobs = None
-    if loss == "masked":
-        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
-                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    knobs = _tap_knobs(loss, alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb)
+    _steps_int(steps, 1)
     rec = S.expand_record(steps, every, record)
     if not rec:
         raise ValueError("record is empty: a rollout objective needs at least one tapped step")
@@ -979,23 +1007,11 @@ def run_rollout_objective_tangent(model: nn.Module, x, steps, target, graph, hid
         x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
         if V is not None:
             V = S._dev_f32(V.detach(), "tangent block")
-        if graph is not None and offsets is None:
-            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
-            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
-                             seed=0 if seed is None else seed, sample_base=sample_base,
-                             offsets=[[] for _ in range(steps)])
-        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                 sample_base=sample_base, offsets=offsets,
-                                 sample_offsets=None if graph is None else graph.sample_offsets)
+        sched = _draw_schedule(x, steps, graph, fire_rate=fire_rate, message_gain=message_gain, nsteps=nsteps,
+                               min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base, offsets=offsets)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-        tgt = target.detach().to(x.device, torch.float32)
-        tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
-        dws, dkeep = None, None
-        if dfields is not None:
-            pairs = [_direction_weights(f) for f in dfields]
-            dws, dkeep = [p[0] for p in pairs], [p[1] for p in pairs]
+        tgt = _tap_target(target, x.device)
+        dws, dkeep = _direction_block(dfields)
         x_final, losses, dlosses, v_final = S.rollout_objective_tangent(
             S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt), w, x, V, K, dweights=dws,
             want_tangents=return_tangents)
@@ -1052,12 +1068,8 @@ def _gauss_newton_front(model: nn.Module, x, steps, target, graph, hidden_only: 
     if loss not in S.TAP_KINDS:
         raise ValueError(f"loss must be one of {sorted(S.TAP_KINDS)}, got {loss!r}")
     _, target = LS._prepare(x[:, :4], target)
-    knobs = None
-    if loss == "masked":
-        knobs = (LS._number(alpha_thr, "alpha_thr"), LS._number(lam_area, "lam_area"),
-                 LS._number(lam_bg_alpha, "lam_bg_alpha"), LS._number(lam_bg_rgb, "lam_bg_rgb"))
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    knobs = _tap_knobs(loss, alpha_thr, lam_area, lam_bg_alpha, lam_bg_rgb)
+    _steps_int(steps, 1)
     rec = S.expand_record(steps, every, record)
     if not rec:
         raise ValueError("record is empty: a Gauss-Newton product needs at least one tapped step")
@@ -1087,25 +1099,15 @@ def run_rollout_gauss_newton(model: nn.Module, x, steps, target, graph, hidden_o
     dfields, target, knobs, rec, scale = _gauss_newton_front(
         model, x, steps, target, graph, hidden_only, dparams, v, every, record, loss, alpha_thr, lam_area,
         lam_bg_alpha, lam_bg_rgb, tap_weights, checkpoint_every)
-    B, C, H, W = x.shape
     with torch.no_grad():
         x = S.check_state(x.detach(), model.n_channels)   # (before the schedule draws its offsets)
         if v is not None:
             v = S._dev_f32(v.detach(), "tangent")
-        if graph is not None and offsets is None:
-            # every other schedule argument is validated before the offsets are drawn (and before a seed is)
-            S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                             message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
-                             seed=0 if seed is None else seed, sample_base=sample_base,
-                             offsets=[[] for _ in range(steps)])
-        sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=x.device, fire_rate=fire_rate,
-                                 message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire, seed=seed,
-                                 sample_base=sample_base, offsets=offsets,
-                                 sample_offsets=None if graph is None else graph.sample_offsets, recompute=True,
-                                 checkpoint_every=checkpoint_every)
+        sched = _draw_schedule(x, steps, graph, fire_rate=fire_rate, message_gain=message_gain, nsteps=nsteps,
+                               min_steps=min_steps, fire=fire, seed=seed, sample_base=sample_base, offsets=offsets,
+                               recompute=True, checkpoint_every=checkpoint_every)
         desc, w, keep, _ = _rollout_desc(model, x, steps, graph, hidden_only, sched)
-        tgt = target.detach().to(x.device, torch.float32)
-        tgt = tgt[:1].contiguous() if tgt.shape[0] == 1 or tgt.stride(0) == 0 else tgt.contiguous()
+        tgt = _tap_target(target, x.device)
         dw, dkeep = (None, None) if dfields is None else _direction_weights(dfields)
         call, taps = S.RolloutCall(desc, sched), S.RolloutTaps(desc, rec, loss, knobs, tgt)
         x_final, tape, fields, losses, dlosses, quad = S.rollout_gn_forward(call, taps, w, x, v, dweights=dw)
@@ -1127,34 +1129,19 @@ def run_gauss_newton_memory(model: nn.Module, x_or_shape, steps: int, graph, hid
     """The shared body of ``gauss_newton_memory``: bytes of the tape, the two workspaces and the fields of the
     product ``rollout_gauss_newton()`` would run for these arguments.  Host-only; Python's and torch's RNG states
     are put back."""
-    import random
-    if isinstance(x_or_shape, torch.Tensor):
-        shape, device = tuple(x_or_shape.shape), x_or_shape.device
-    else:
-        shape = tuple(int(t) for t in x_or_shape)
-        given = nsteps if nsteps is not None else fire
-        device = given.device if isinstance(given, torch.Tensor) else torch.device("cpu")
-    if len(shape) != 4:
-        raise ValueError(f"state must be [B,C,H,W], got {shape}")
-    if shape[1] != model.n_channels:
-        raise ValueError(f"state has {shape[1]} channels, model expects {model.n_channels}")
+    shape, device = _shape_and_device(model, x_or_shape, nsteps, fire)
     B, C, H, W = shape
     _tangent_flags(model, graph, hidden_only)
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive int, got {steps!r}")
+    _steps_int(steps, 1)
     rec = S.expand_record(steps, every, record)
     if not rec:
         raise ValueError("record is empty: a Gauss-Newton product needs at least one tapped step")
-    py_state, torch_state = random.getstate(), torch.get_rng_state()
-    try:
+    with _rng_restored():
         sched = S.build_schedule(steps=steps, B=B, H=H, W=W, device=device, fire_rate=fire_rate,
                                  message_gain=message_gain, nsteps=nsteps, min_steps=min_steps, fire=fire,
                                  seed=seed, sample_base=sample_base, offsets=offsets,
                                  sample_offsets=None if graph is None else graph.sample_offsets,
                                  recompute=True, checkpoint_every=checkpoint_every)
-    finally:
-        random.setstate(py_state)
-        torch.set_rng_state(torch_state)
     desc, _ = _rollout_desc_host(model, shape, steps, graph, hidden_only, sched)
     # (the sizes do not depend on the loss kind or on the target: a one-float placeholder stands for it)
     taps = S.RolloutTaps(desc, rec, "premult", None, torch.zeros(1, 4, 1, 1))

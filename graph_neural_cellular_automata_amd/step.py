@@ -115,6 +115,68 @@ _WS_BYTES: dict = {}
 SUPPORT_SET = "supported: 4 <= C <= 32; hidden <= 128, or hidden <= 256 for 13 <= C <= 16"
 
 
+def _entry(name: str):
+    """The library's entry point ``name``; a library built before it was added names what is missing."""
+    fn = getattr(L.load(), name, None)
+    if fn is None:
+        raise L.GncaError(f"libgnca.so at {L.LIB_PATH} has no {name}: rebuild it (python -c 'import __graft_entry__ "
+                          f"as g; g.build(force=True)')")
+    return fn
+
+
+def _sized(n: int, what: str, desc, device=None, extra: str = "", K=None):
+    """The uint8 workspace for a size query's answer ``n`` (``device`` None: ``n`` itself).  0 is the query's
+    refusal: ``GncaError`` "unsupported ``what``: [K=..] B=.. (the support set``extra``)"."""
+    if n == 0:
+        k = "" if K is None else f"K={K} "
+        raise L.GncaError(f"unsupported {what}: {k}B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
+                          f"hidden={desc.hidden} ({SUPPORT_SET}{extra})")
+    return n if device is None else torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _k1_info(desc) -> tuple[str, int]:
+    """(kernel name, arith bits) of gnca_k1_variant for ``desc``."""
+    buf = ctypes.create_string_buffer(128)
+    arith = ctypes.c_int32(0)
+    L.check(L.load().gnca_k1_variant(ctypes.byref(desc), buf, 128, ctypes.byref(arith)), "gnca_k1_variant")
+    return buf.value.decode(), arith.value
+
+
+def _flat_offsets(desc, steps: int, offsets_per_step: list):
+    """``offsets_per_step`` as the int8 array [steps][k][2] of the C calls, or None when there are none."""
+    flat = [v for offs in offsets_per_step for o in offs for v in o]
+    if (desc.flags & L.GRAPH) and desc.num_offsets > 0 and len(flat) != steps * 2 * desc.num_offsets:
+        raise ValueError("offsets_per_step must hold k pairs for every step")
+    return (ctypes.c_int8 * len(flat))(*flat) if flat else None
+
+
+def _records(record: list):
+    """The recorded step indices as an int32 array (one unused element when there are none)."""
+    return (ctypes.c_int32 * max(1, len(record)))(*record)
+
+
+def _grad_buffers(want: dict | None, out: dict | None, device):
+    """(``L.Grads``, {name: tensor}) for the ``want``ed parameters: the caller's ``out`` tensors where given,
+    fresh float32 ones elsewhere."""
+    g, grads = L.Grads(), {}
+    given = out or {}
+    for name, p in (want or {}).items():
+        t = given.get(name)
+        if t is None:
+            t = torch.empty(p.shape, dtype=torch.float32, device=device)
+        elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
+        grads[name] = t
+        setattr(g, GRAD_FIELDS[name], t.data_ptr())
+    return g, grads
+
+
+def _tape(call: "RolloutCall", device) -> torch.Tensor:
+    """The tape of ``call``'s schedule (0 steps record nothing: 256 bytes keep the pointer valid)."""
+    nb = L.load().gnca_rollout_tape_bytes(ctypes.byref(call.desc), ctypes.byref(call.c))
+    return torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+
+
 def workspace(desc: L.StepDesc, device) -> torch.Tensor:
     # the size depends on the shape class and the offsets' radius (the tile plan), not on the
     # offsets themselves or the knobs' values
@@ -128,20 +190,14 @@ def workspace(desc: L.StepDesc, device) -> torch.Tensor:
         n = L.load().gnca_workspace_bytes(ctypes.byref(desc))
         if n and len(_WS_BYTES) < 256:
             _WS_BYTES[key] = n
-    if n == 0:
-        raise L.GncaError(
-            f"unsupported step shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-            f"hidden={desc.hidden} ({SUPPORT_SET})")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _sized(n, "step shape", desc, device)
 
 
 def k1_variant(desc: L.StepDesc) -> tuple[str, str]:
     """(kernel name, MFMA arithmetic) of the K1 the plan for ``desc`` launches: arithmetic "f32"
     (fp32 MFMA) or "bf16x6" (bf16 MFMA on exact 3-way splits, 6 products per fp32 product)."""
-    buf = ctypes.create_string_buffer(128)
-    arith = ctypes.c_int32(0)
-    L.check(L.load().gnca_k1_variant(ctypes.byref(desc), buf, 128, ctypes.byref(arith)), "gnca_k1_variant")
-    return buf.value.decode(), ("bf16x6" if arith.value & 1 else "f32")
+    name, arith = _k1_info(desc)
+    return name, ("bf16x6" if arith & 1 else "f32")
 
 
 def bb_variant(desc: L.StepDesc) -> str:
@@ -168,19 +224,13 @@ def k2_variant(desc: L.StepDesc, co: int = 0) -> str:
 def rollout_compact(desc: L.StepDesc) -> bool:
     """True when a rollout of ``desc``'s shape runs on the compact update field (K1 packs the live
     cells' dx per tile, K2 unpacks them: GNCA_PHASE_COMPACT)."""
-    buf = ctypes.create_string_buffer(128)
-    arith = ctypes.c_int32(0)
-    L.check(L.load().gnca_k1_variant(ctypes.byref(desc), buf, 128, ctypes.byref(arith)), "gnca_k1_variant")
-    return bool(arith.value & 2)
+    return bool(_k1_info(desc)[1] & 2)
 
 
 def rollout_subs(desc: L.StepDesc) -> int:
     """Concurrent sub-batches a rollout of ``desc``'s shape runs as (2: one sub-batch's K2 beside
     the other's K1 on two streams; 1: one stream)."""
-    buf = ctypes.create_string_buffer(128)
-    arith = ctypes.c_int32(0)
-    L.check(L.load().gnca_k1_variant(ctypes.byref(desc), buf, 128, ctypes.byref(arith)), "gnca_k1_variant")
-    return 2 if arith.value & 4 else 1
+    return 2 if _k1_info(desc)[1] & 4 else 1
 
 
 def rollout_fold(desc: L.StepDesc, possible: bool = False) -> bool:
@@ -188,10 +238,7 @@ def rollout_fold(desc: L.StepDesc, possible: bool = False) -> bool:
     residual, post-update alpha gate) into the next step's K1, so one K1 launch per step plus one
     K2 at the end of the rollout (gnca_k1_variant arith bit 8).  ``possible``: whether it can, on
     request (``rollout(..., fold=True)``; arith bit 16) where it is not the default."""
-    buf = ctypes.create_string_buffer(128)
-    arith = ctypes.c_int32(0)
-    L.check(L.load().gnca_k1_variant(ctypes.byref(desc), buf, 128, ctypes.byref(arith)), "gnca_k1_variant")
-    return bool(arith.value & (16 if possible else 8))
+    return bool(_k1_info(desc)[1] & (16 if possible else 8))
 
 
 _MULTI_GPU = None
@@ -300,11 +347,7 @@ def rollout(desc, weights, x, steps: int, offsets_per_step: list, fold: bool = F
     """``steps`` no-grad steps (GNCA_FIRE_HASH / NONE) in one C call.  ``fold``: fold each step's
     finish into the next K1 even where that is not the default (GNCA_ROLLOUT_FOLD)."""
     lib = L.load()
-    k = desc.num_offsets
-    flat = [v for offs in offsets_per_step for o in offs for v in o]
-    if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
-        raise ValueError("offsets_per_step must hold k pairs for every step")
-    arr = (ctypes.c_int8 * max(1, len(flat)))(*flat) if flat else None
+    arr = _flat_offsets(desc, steps, offsets_per_step)
     out = torch.empty_like(x)
     scratch = torch.empty_like(x)
     ws = workspace(desc, x.device)
@@ -337,22 +380,8 @@ def step_backward(desc, weights, x, gy, fire=None, want: dict | None = None, sav
     lib = L.load()
     gy = _dev_f32(gy, "grad_output")
     gx = torch.empty_like(x)
-    g = L.Grads()
-    given, out = out or {}, {}
-    for name, p in (want or {}).items():
-        t = given.get(name)
-        if t is None:
-            t = torch.empty(p.shape, dtype=torch.float32, device=x.device)
-        elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
-        out[name] = t
-        setattr(g, GRAD_FIELDS[name], t.data_ptr())
-    n = lib.gnca_bwd_workspace_bytes(ctypes.byref(desc))
-    if n == 0:
-        raise L.GncaError(
-            f"unsupported step shape for the backward: B={desc.B} C={desc.C} H={desc.H} "
-            f"W={desc.W} hidden={desc.hidden} ({SUPPORT_SET})")
-    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    g, out = _grad_buffers(want, out, x.device)
+    ws = _sized(lib.gnca_bwd_workspace_bytes(ctypes.byref(desc)), "step shape for the backward", desc, x.device)
     act = _active_u8(active, desc.B, x.device)
     rc = lib.gnca_step_bwd_f32(ctypes.byref(desc), ctypes.byref(weights), x.data_ptr(), _ptr(fire),
                                _ptr(act), gy.data_ptr(), gx.data_ptr(), ctypes.byref(g), _ptr(saved),
@@ -576,13 +605,9 @@ def trace(desc, weights, x, steps: int, offsets_per_step: list, record: list, ch
     """``steps`` no-grad steps in one C call that also records (gnca_rollout_trace_f32): returns
     ``(x_final, frames [R,B,channels,H,W], attention [R,B,H,W] or None)``."""
     lib = L.load()
-    k = desc.num_offsets
-    flat = [v for offs in offsets_per_step for o in offs for v in o]
-    if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
-        raise ValueError("offsets_per_step must hold k pairs for every step")
-    arr = (ctypes.c_int8 * len(flat))(*flat) if flat else None
+    arr = _flat_offsets(desc, steps, offsets_per_step)
     R = len(record)
-    rec = (ctypes.c_int32 * max(1, R))(*record)
+    rec = _records(record)
     out = torch.empty_like(x)
     frames = torch.empty(R, desc.B, channels, desc.H, desc.W, dtype=torch.float32, device=x.device)
     attn = torch.empty(R, desc.B, desc.H, desc.W, dtype=torch.float32, device=x.device) if want_attention else None
@@ -593,11 +618,8 @@ def trace(desc, weights, x, steps: int, offsets_per_step: list, record: list, ch
     # (an empty tensor's data_ptr is 0: no record points, nothing is written)
     a.frames = frames.data_ptr() if R else None
     a.attn = attn.data_ptr() if (attn is not None and R) else None
-    n = lib.gnca_rollout_trace_workspace_bytes(ctypes.byref(desc), ctypes.byref(a))
-    if n == 0:
-        raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET})")
-    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    ws = _sized(lib.gnca_rollout_trace_workspace_bytes(ctypes.byref(desc), ctypes.byref(a)), "trace shape", desc,
+                x.device)
     rc = lib.gnca_rollout_trace_f32(ctypes.byref(desc), ctypes.byref(weights), ctypes.byref(a), x.data_ptr(),
                                     out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(x.device))
     L.check(rc, "gnca_rollout_trace_f32")
@@ -643,16 +665,12 @@ def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels,
     """The shared body of ``trace_metrics`` (``diag_taps`` None), ``trace_diag`` (``diag_taps``: whether
     the per-offset stack is recorded too) and ``trace_vitals`` (``vitals_thr`` set, beside either)."""
     lib = L.load()
-    fn = _diag_entry("gnca_rollout_trace_diag") if diag_taps is not None else None
+    fn = _entry("gnca_rollout_trace_diag") if diag_taps is not None else None
     if vitals_thr is not None:
-        fn = _diag_entry("gnca_rollout_trace_vitals")
-    k = desc.num_offsets
-    flat = [v for offs in offsets_per_step for o in offs for v in o]
-    if (desc.flags & L.GRAPH) and k > 0 and len(flat) != steps * 2 * k:
-        raise ValueError("offsets_per_step must hold k pairs for every step")
-    arr = (ctypes.c_int8 * len(flat))(*flat) if flat else None
+        fn = _entry("gnca_rollout_trace_vitals")
+    arr = _flat_offsets(desc, steps, offsets_per_step)
     R = len(record)
-    rec = (ctypes.c_int32 * max(1, R))(*record)
+    rec = _records(record)
     out = torch.empty_like(x)
     frames = None
     if want_frames:
@@ -678,10 +696,7 @@ def _trace_measured(desc, weights, x, steps, offsets_per_step, record, channels,
         size = (lib.gnca_rollout_trace_metrics_workspace_bytes if fn is None
                 else lib.gnca_rollout_trace_diag_workspace_bytes)
         n = size(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(m))
-    if n == 0:
-        raise L.GncaError(f"unsupported trace shape: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET})")
-    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    ws = _sized(n, "trace shape", desc, x.device)
     if vitals_thr is not None:
         vit = torch.empty(R, desc.B, len(L.VITALS_FIELDS), dtype=torch.float64, device=x.device)
         v = L.TraceVitals()
@@ -741,13 +756,6 @@ class GraphDiagnostics:
         return "GraphDiagnostics(" + ", ".join(f"{n}={shape(getattr(self, n))}" for n in L.DIAG_FIELDS) + ")"
 
 
-def _diag_entry(name: str):
-    fn = getattr(L.load(), name, None)
-    if fn is None:
-        raise L.GncaError(f"libgnca.so lacks {name}: rebuild it")
-    return fn
-
-
 def _diag_buffers(desc, device, per_offset: bool, lead: tuple = ()):
     """The output tensors of one diagnostics call (``lead``: a trace's record axis) and their struct."""
     B, H, W = desc.B, desc.H, desc.W
@@ -773,7 +781,7 @@ def _diag_buffers(desc, device, per_offset: bool, lead: tuple = ()):
 def graph_diagnostics(desc, weights, x, per_offset: bool = True) -> GraphDiagnostics:
     """The diagnostics of state ``x`` for ``desc``'s offsets (gnca_graph_diag): a side computation, no
     step."""
-    fn = _diag_entry("gnca_graph_diag")
+    fn = _entry("gnca_graph_diag")
     lib = L.load()
     t, o = _diag_buffers(desc, x.device, per_offset)
     n = lib.gnca_graph_diag_workspace_bytes(ctypes.byref(desc))
@@ -820,22 +828,13 @@ class RolloutCall:
         self.c = c
 
     def _sizes(self, fn):
-        n = fn(ctypes.byref(self.desc), ctypes.byref(self.c))
-        if n == 0:
-            d = self.desc
-            raise L.GncaError(f"unsupported rollout shape: B={d.B} C={d.C} H={d.H} W={d.W} hidden={d.hidden} "
-                              f"({SUPPORT_SET})")
-        return n
+        return _sized(fn(ctypes.byref(self.desc), ctypes.byref(self.c)), "rollout shape", self.desc)
 
     def forward(self, weights, x, want_tape: bool):
         """(x_final, tape or None).  ``want_tape=False`` is the no-grad form of the same schedule."""
         lib = L.load()
         out = torch.empty_like(x)
-        tape = None
-        if want_tape:
-            # (0 steps record nothing: a 256-byte tape keeps the pointer valid)
-            nb = lib.gnca_rollout_tape_bytes(ctypes.byref(self.desc), ctypes.byref(self.c))
-            tape = torch.empty(max(nb, 256), dtype=torch.uint8, device=x.device)
+        tape = _tape(self, x.device) if want_tape else None
         ws = torch.empty(self._sizes(lib.gnca_rollout_fwd_workspace_bytes), dtype=torch.uint8, device=x.device)
         rc = lib.gnca_rollout_fwd_f32(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c),
                                       x.data_ptr(), out.data_ptr(), _ptr(tape), 0 if tape is None else tape.numel(),
@@ -855,14 +854,11 @@ class RolloutCall:
         """(x_final, tape or None, losses [R,B], alive_count [B] or None): ``forward`` that also writes
         the losses of the tapped states as they are produced (``gnca_rollout_fwd_taps``), so it serves
         a checkpointed tape, which holds few of them, and the no-grad form, which has no tape."""
-        fn = _tap_entry("gnca_rollout_fwd_taps")
+        fn = _entry("gnca_rollout_fwd_taps")
         lib = L.load()
         B, dev = self.desc.B, x.device
         out = torch.empty_like(x)
-        tape = None
-        if want_tape:
-            nb = lib.gnca_rollout_tape_bytes(ctypes.byref(self.desc), ctypes.byref(self.c))
-            tape = torch.empty(max(nb, 256), dtype=torch.uint8, device=dev)
+        tape = _tape(self, dev) if want_tape else None
         losses = torch.empty(taps.c.n, B, dtype=torch.float32, device=dev)
         alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
         ws = torch.empty(self._sizes(lib.gnca_rollout_fwd_workspace_bytes), dtype=torch.uint8, device=dev)
@@ -879,16 +875,7 @@ class RolloutCall:
         lib = L.load()
         gy = _dev_f32(gy, "grad_output")
         gx = torch.empty_like(gy)
-        g = L.Grads()
-        given, grads = out or {}, {}
-        for name, p in (want or {}).items():
-            t = given.get(name)
-            if t is None:
-                t = torch.empty(p.shape, dtype=torch.float32, device=gy.device)
-            elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
-            grads[name] = t
-            setattr(g, GRAD_FIELDS[name], t.data_ptr())
+        g, grads = _grad_buffers(want, out, gy.device)
         ws = torch.empty(self._sizes(lib.gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=gy.device)
         rc = lib.gnca_rollout_bwd_f32(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c),
                                       tape.data_ptr(), tape.numel(), gy.data_ptr(), gx.data_ptr(), ctypes.byref(g),
@@ -903,7 +890,7 @@ class RolloutCall:
     def tap_losses(self, taps: "RolloutTaps", tape, x_final):
         """(losses [R,B], alive_count [B] or None) of the tapped states of the rollout that recorded
         ``tape`` and returned ``x_final``."""
-        fn = _tap_entry("gnca_rollout_tap_loss")
+        fn = _entry("gnca_rollout_tap_loss")
         B, dev = self.desc.B, x_final.device
         losses = torch.empty(taps.c.n, B, dtype=torch.float32, device=dev)
         alive = torch.empty(B, dtype=torch.int32, device=dev) if taps.c.kind == L.TAP_MASKED else None
@@ -917,7 +904,7 @@ class RolloutCall:
                       want: dict | None = None, out: dict | None = None):
         """(gx, {name: grad}) of ``sum(g_losses * losses) + sum(gy * x_final)``; either cotangent may be
         None (not both).  ``want`` / ``out`` as in ``backward``."""
-        fn = _tap_entry("gnca_rollout_bwd_taps")
+        fn = _entry("gnca_rollout_bwd_taps")
         if gy is None and g_losses is None:
             raise ValueError("backward_taps needs gy, g_losses or both")
         dev = x_final.device
@@ -927,16 +914,7 @@ class RolloutCall:
             if tuple(g_losses.shape) != (taps.c.n, self.desc.B):
                 raise ValueError(f"grad_losses must be [{taps.c.n},{self.desc.B}], got {tuple(g_losses.shape)}")
         gx = torch.empty_like(x_final)
-        g = L.Grads()
-        given, grads = out or {}, {}
-        for name, p in (want or {}).items():
-            t = given.get(name)
-            if t is None:
-                t = torch.empty(p.shape, dtype=torch.float32, device=dev)
-            elif t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"gradient buffer for {name} must be contiguous float32 {tuple(p.shape)}")
-            grads[name] = t
-            setattr(g, GRAD_FIELDS[name], t.data_ptr())
+        g, grads = _grad_buffers(want, out, dev)
         ws = torch.empty(self._sizes(L.load().gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=dev)
         taps.c.stream = stream_ptr(dev)
         rc = fn(ctypes.byref(self.desc), ctypes.byref(weights), ctypes.byref(self.c), ctypes.byref(taps.c),
@@ -944,13 +922,6 @@ class RolloutCall:
                 gx.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel())
         L.check(rc, "gnca_rollout_bwd_taps")
         return gx, grads
-
-
-def _tap_entry(name: str):
-    fn = getattr(L.load(), name, None)
-    if fn is None:
-        raise L.GncaError(f"libgnca.so at {L.LIB_PATH} has no {name}; rebuild it")
-    return fn
 
 
 TAP_KINDS = {"premult": L.TAP_PREMULT, "masked": L.TAP_MASKED}
@@ -967,7 +938,7 @@ class RolloutTaps:
             raise ValueError("a rollout objective needs at least one tapped step")
         c = L.RolloutTaps()
         c.n = len(record)
-        arr = (ctypes.c_int32 * len(record))(*record)
+        arr = _records(record)
         c.steps = ctypes.cast(arr, ctypes.c_void_p)
         c.kind = TAP_KINDS[kind]
         c.masked.B, c.masked.H, c.masked.W = desc.B, desc.H, desc.W
@@ -986,14 +957,6 @@ ZERO_PAD_TANGENT = ("the tangent of the zero-padded shift is not implemented: it
                     "build the model with graph_zero_padded_shift=False (torus mode)")
 
 
-def _tangent_entry(name: str):
-    fn = getattr(L.load(), name, None)
-    if fn is None:
-        raise L.GncaError(f"libgnca.so has no {name}: rebuild it (python -c 'import __graft_entry__ as g; "
-                          f"g.build(force=True)')")
-    return fn
-
-
 def check_tangent_desc(flags: int, num_offsets: int) -> None:
     """ValueError for what the tangent entry points refuse, before anything is drawn or launched."""
     if (flags & L.GRAPH) and (flags & L.ZERO_PAD_SHIFT) and num_offsets > 0:
@@ -1010,15 +973,12 @@ DIRECTION_FIELDS = {"update_net.0.weight": "w1", "update_net.0.bias": "b1", "upd
 def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None, dweights=None):
     """One step and its Jacobian-vector product: (x_out, v_out), x_out bitwise ``step``'s.  ``dweights``: a
     ``Weights`` struct holding a parameter direction (``gnca_step_tangent_params``)."""
-    fn = _tangent_entry("gnca_step_tangent" if dweights is None else "gnca_step_tangent_params")
+    fn = _entry("gnca_step_tangent" if dweights is None else "gnca_step_tangent_params")
     lib = L.load()
     x_out, v_out = torch.empty_like(x), torch.empty_like(v)
     if ws is None:
-        n = lib.gnca_step_tangent_workspace_bytes(ctypes.byref(desc))
-        if n == 0:
-            raise L.GncaError(f"unsupported tangent step: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                              f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
-        ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+        ws = _sized(lib.gnca_step_tangent_workspace_bytes(ctypes.byref(desc)), "tangent step", desc, x.device,
+                    "; torus mode")
     act = _active_u8(active, desc.B, x.device)
     dw = () if dweights is None else (ctypes.byref(dweights),)
     rc = fn(ctypes.byref(desc), ctypes.byref(weights), *dw, x.data_ptr(), _ptr(fire), _ptr(act), v.data_ptr(),
@@ -1030,22 +990,19 @@ def step_tangent(desc, weights, x, v, fire=None, active=None, ws=None, dweights=
 def rollout_tangent(call: "RolloutCall", weights, x, v, record: list, renormalize: bool, dweights=None):
     """(x_final, v_final, log_norm float64 [R,B]) of the schedule bound in ``call``.  ``dweights``: a ``Weights``
     struct holding a parameter direction (``gnca_rollout_tangent_params``)."""
-    fn = _tangent_entry("gnca_rollout_tangent" if dweights is None else "gnca_rollout_tangent_params")
+    fn = _entry("gnca_rollout_tangent" if dweights is None else "gnca_rollout_tangent_params")
     lib = L.load()
     desc, dev = call.desc, x.device
     a = L.TangentArgs()
     a.num_records = len(record)
-    arr = (ctypes.c_int32 * max(1, len(record)))(*record)
+    arr = _records(record)
     a.record = ctypes.cast(arr, ctypes.c_void_p) if record else None
     a.flags = L.TANGENT_RENORM if renormalize else 0
     log_norm = torch.empty(len(record), desc.B, dtype=torch.float64, device=dev)
     a.log_norm = log_norm.data_ptr() if record else None
     a.stream = stream_ptr(dev)
     n = lib.gnca_rollout_tangent_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(a))
-    if n == 0:
-        raise L.GncaError(f"unsupported tangent rollout: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
-    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = _sized(n, "tangent rollout", desc, dev, "; torus mode")
     x_final, v_final = torch.empty_like(x), torch.empty_like(v)
     dw = () if dweights is None else (ctypes.byref(dweights),)
     rc = fn(ctypes.byref(desc), ctypes.byref(weights), *dw, ctypes.byref(call.c), ctypes.byref(a), x.data_ptr(),
@@ -1061,7 +1018,7 @@ def tangent_qr(v, want_r: bool = True, ws=None):
     """The thin QR of the block ``v`` [K,B,...] (float32, contiguous, on the GPU), IN PLACE: ``v`` becomes Q.
     Returns (r float64 [B,K,K] or None, log_diag float64 [B,K], ws); the workspace begins with the Gram
     partials, float64 [B][nchunk][K(K+1)/2] (include/gnca.h)."""
-    fn = _tangent_entry("gnca_tangent_qr")
+    fn = _entry("gnca_tangent_qr")
     lib = L.load()
     K, B = v.shape[0], v.shape[1]
     n = v[0, 0].numel()
@@ -1081,24 +1038,21 @@ def tangent_qr(v, want_r: bool = True, ws=None):
 def rollout_tangent_block(call: "RolloutCall", weights, x, v, record: list, orthonormalize: bool, dweights=None):
     """(x_final, v_final [K,B,C,H,W], log_r float64 [R,B,K]) of the schedule bound in ``call``.  ``dweights``: K
     ``Weights`` structs, direction j's parameter direction (``gnca_rollout_tangent_block_params``)."""
-    fn = _tangent_entry("gnca_rollout_tangent_block" if dweights is None else "gnca_rollout_tangent_block_params")
+    fn = _entry("gnca_rollout_tangent_block" if dweights is None else "gnca_rollout_tangent_block_params")
     lib = L.load()
     desc, dev = call.desc, x.device
     K = v.shape[0]
     a = L.TangentBlockArgs()
     a.num_dirs = K
     a.num_records = len(record)
-    arr = (ctypes.c_int32 * max(1, len(record)))(*record)
+    arr = _records(record)
     a.record = ctypes.cast(arr, ctypes.c_void_p) if record else None
     a.flags = L.TBLOCK_ORTHO if orthonormalize else 0
     log_r = torch.empty(len(record), desc.B, K, dtype=torch.float64, device=dev)
     a.log_r = log_r.data_ptr() if record else None
     a.stream = stream_ptr(dev)
     n = lib.gnca_rollout_tangent_block_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(a))
-    if n == 0:
-        raise L.GncaError(f"unsupported tangent block rollout: K={K} B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
-    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = _sized(n, "tangent block rollout", desc, dev, "; torus mode", K=K)
     x_final, v_final = torch.empty_like(x), torch.empty_like(v)
     dw = ()
     if dweights is not None:
@@ -1119,7 +1073,7 @@ def rollout_objective_tangent(call: "RolloutCall", taps: "RolloutTaps", weights,
     """(x_final, losses float32 [R,B], dlosses float64 [R,K,B], v_final [K,B,C,H,W] or None) of the schedule
     bound in ``call``.  ``v``: the block [K,B,C,H,W] or None (zeros, made on the device); ``dweights``: K
     ``Weights`` structs or None."""
-    fn = _tangent_entry("gnca_rollout_objective_tangent")
+    fn = _entry("gnca_rollout_objective_tangent")
     lib = L.load()
     desc, dev = call.desc, x.device
     R, B = taps.c.n, desc.B
@@ -1128,10 +1082,7 @@ def rollout_objective_tangent(call: "RolloutCall", taps: "RolloutTaps", weights,
     taps.c.stream = stream_ptr(dev)
     n = lib.gnca_rollout_objective_tangent_workspace_bytes(ctypes.byref(desc), ctypes.byref(call.c),
                                                            ctypes.byref(taps.c), K)
-    if n == 0:
-        raise L.GncaError(f"unsupported objective tangent rollout: K={K} B={B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode)")
-    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = _sized(n, "objective tangent rollout", desc, dev, "; torus mode", K=K)
     x_final = torch.empty_like(x)
     v_final = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=dev) if want_tangents else None
     losses = torch.empty(R, B, dtype=torch.float32, device=dev)
@@ -1151,13 +1102,11 @@ def rollout_objective_tangent(call: "RolloutCall", taps: "RolloutTaps", weights,
 # ---------------------------------------------------------------------------------------------
 def gn_memory(call: "RolloutCall", taps: "RolloutTaps") -> dict:
     """Bytes of one Gauss-Newton product of the schedule bound in ``call``, from the host-only size queries."""
-    fn = _tangent_entry("gnca_rollout_gn_fwd_workspace_bytes")
+    fn = _entry("gnca_rollout_gn_fwd_workspace_bytes")
     lib = L.load()
     desc = call.desc
-    n = fn(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(taps.c))
-    if n == 0:
-        raise L.GncaError(f"unsupported Gauss-Newton rollout: B={desc.B} C={desc.C} H={desc.H} W={desc.W} "
-                          f"hidden={desc.hidden} ({SUPPORT_SET}; torus mode; a states-only tape)")
+    n = _sized(fn(ctypes.byref(desc), ctypes.byref(call.c), ctypes.byref(taps.c)), "Gauss-Newton rollout", desc,
+               extra="; torus mode; a states-only tape")
     return {"tape": lib.gnca_rollout_tape_bytes(ctypes.byref(desc), ctypes.byref(call.c)),
             "forward_workspace": n,
             "backward_workspace": call._sizes(lib.gnca_rollout_bwd_workspace_bytes),
@@ -1168,7 +1117,7 @@ def rollout_gn_forward(call: "RolloutCall", taps: "RolloutTaps", weights, x, v, 
     """(x_final, tape, fields float32 [R,B,4,H,W], losses float32 [R,B], dlosses float64 [R,B], quad float64 [R,B])
     of the schedule bound in ``call`` (``recompute=True``).  ``v``: [B,C,H,W] or None (zeros, made on the device);
     ``dweights``: a ``Weights`` struct holding the parameter direction, or None."""
-    fn = _tangent_entry("gnca_rollout_gn_fwd")
+    fn = _entry("gnca_rollout_gn_fwd")
     desc, dev = call.desc, x.device
     R, B = taps.c.n, desc.B
     taps.c.stream = stream_ptr(dev)
@@ -1194,18 +1143,13 @@ def rollout_gn_backward(call: "RolloutCall", taps: "RolloutTaps", weights, tape,
     """(gx, {name: grad}) of the BPTT that injects ``scale[r] * fields[r]`` at tap r on the tape of
     ``rollout_gn_forward``.  ``scale``: R host numbers; ``like``: a tensor of the state's shape; ``want`` as in
     ``RolloutCall.backward``."""
-    fn = _tangent_entry("gnca_rollout_gn_bwd")
+    fn = _entry("gnca_rollout_gn_bwd")
     dev = fields.device
     if len(scale) != taps.c.n:
         raise ValueError(f"{len(scale)} scales for {taps.c.n} taps")
     sc = (ctypes.c_float * len(scale))(*scale)
     gx = torch.empty_like(like)
-    g = L.Grads()
-    grads = {}
-    for name, p in (want or {}).items():
-        t = torch.empty(p.shape, dtype=torch.float32, device=dev)
-        grads[name] = t
-        setattr(g, GRAD_FIELDS[name], t.data_ptr())
+    g, grads = _grad_buffers(want, None, dev)
     ws = torch.empty(call._sizes(L.load().gnca_rollout_bwd_workspace_bytes), dtype=torch.uint8, device=dev)
     taps.c.stream = stream_ptr(dev)
     rc = fn(ctypes.byref(call.desc), ctypes.byref(weights), ctypes.byref(call.c), ctypes.byref(taps.c),
